@@ -10,12 +10,15 @@ for N > 1 the RCCL all-gather of the per-rank certificate-verdict bitmaps
 Headline (default --config c4): BASELINE.json config C4, the 16M-grant
 certificate batch (R = 4).  It fits one MI355X, so N = 1 verifies all of it;
 N > 1 shards its certificate-index range contiguously over the ranks (strong
-scaling: 16M/N grants per GPU) and all-gathers the verdict bitmaps.  At N = 1
-the run also reports a C3 leg (4M grants, R = 7, server and client
-predicates, own roofline), the PCIe-inclusive host path, the Write2ToServer
-wire path, producer signing and the CPU baseline.
+scaling: 16M/N grants per GPU) and all-gathers the verdict bitmaps.  A plain
+run sets up, warms up, times the K steps and prints the result line.  With
+--full an N = 1 run also reports a C3 leg (4M grants, R = 7, server and client
+predicates, own roofline), the per-rank shard sizes, the separate-copies
+layout, the PCIe-inclusive host path, the Write2ToServer wire path with the
+batcher legs, producer signing, the in-process cluster and the CPU baseline.
+--dump-outputs DIR writes the last timed step's verdict arrays to DIR/*.npy.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -24,6 +27,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -83,9 +87,17 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-wire", action="store_true", help="skip the Write2ToServer wire-path measurement")
     ap.add_argument("--no-c3", action="store_true", help="skip the C3 leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side leg (CPU baseline, C3, shard sizes, separate copies, host / wire / "
+                         "batcher paths, signing, cluster) and the grant-prep dedup count; a plain run only sets "
+                         "up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's verdict arrays to DIR/<name>.npy")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed device-resident steps (no side legs): the profiled run")
-    ap.add_argument("--cache-dir", default=os.environ.get("MOCHI_CACHE", "/tmp/mochi_bench_cache"))
+                    help="only the timed device-resident steps even with --full (the profiled run)")
+    ap.add_argument("--cache-dir", default=os.environ.get("MOCHI_CACHE") or os.path.join(
+        tempfile.gettempdir(), f"mochi_bench_cache_{os.getuid()}"),
+                    help="scratch files of the --full legs (per user: another user's directory is not writable)")
     ap.add_argument("--no-native", action="store_true", help="skip the native batcher load driver leg")
     ap.add_argument("--no-cluster", action="store_true", help="skip the in-process cluster (C1 / C5 proxy) leg")
     ap.add_argument("--no-shard-sizes", action="store_true", help="skip the per-rank shard-size leg (16M/2, /4, /8)")
@@ -196,6 +208,35 @@ def roofline(n_grants, pow_ms, traffic=None):
                         "frac": round(mfma / INT8_DENSE_PEAK, 4)},
             "cios_equiv": {"tmac_per_s": round(cios / 1e12, 3),
                            "vs_valu_only_peak": round(cios / PEAK_MAC_PER_S, 4)}}
+
+
+DUMP_SAMPLE = 1 << 19  # elements kept per array: 10 arrays x 512Ki x 8 B = 40 MiB at the most
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, host, gathered=None):
+    """--dump-outputs: the verdict arrays of the last timed step (what a caller of
+    verify_device reads back: DeviceVerdicts.NAMES, plus the all-gathered batch
+    bitmap at N > 1) as out_dir/<name>.npy.  8-bit arrays go out as float32, the
+    32- and 64-bit ones as float64 (exact below 2^53).  An array longer than
+    DUMP_SAMPLE is cut to a fixed, seeded sample of its elements (sorted indices
+    from DUMP_SEED and the array's length), so two builds given the same
+    arguments write the same elements of the same inputs' verdicts."""
+    import numpy as np
+
+    import mochi_hip as mh
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: getattr(host, name) for name in mh.DeviceVerdicts.NAMES}
+    arrays["gathered_cert_accept_bits"] = gathered
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.asarray(a).reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            idx = np.random.default_rng([DUMP_SEED, a.size]).choice(a.size, DUMP_SAMPLE, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64))
 
 
 def _free_port():
@@ -324,12 +365,13 @@ def main():
     cpu_flags = os.path.join(args.cache_dir, "cpu_baseline_flags.npz")
     batch_file = os.path.join(args.cache_dir, f"bench_batch_{os.getpid()}.npz")
     cpu_certs = min(C, 250_000)  # the baseline's sample: the stream's first certificates (~1M grants at R = 4)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    extras = world == 1 and args.full and not args.headline_only  # side measurements: --full single-GPU runs only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_child = start_cpu_baseline(args, R, k, cpu_flags, batch_file)
     # native batcher load driver (microbench/batcher_load): also started before this
     # process touches the GPU; it waits for the Write2 input file the wire leg writes
     args.native_child = args.native_input = None
-    if rank == 0 and world == 1 and not (args.headline_only or args.no_wire or args.no_native):
+    if rank == 0 and extras and not (args.no_wire or args.no_native):
         args.native_input = os.path.join(args.cache_dir, f"w2_native_{os.getpid()}.bin")
         args.native_child = start_batcher_native(args, args.native_input)
     torch.cuda.set_device(local_rank)
@@ -379,15 +421,18 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # correctness gate on this rank's shard (ground truth of the seeded fault mix)
-    host = out.to_host()
-    flags_ok = bool(np.array_equal(host.grant_flags, synth.expected_flags))
 
     ver.set_profiling(True)
     ev_s, wall = timed_steps(step, args.steps, 0, stream, dist)
     ver.set_profiling(False)
     prof = ver.read_profile()
     stage_ms = [prof[name] for name in ver.STAGES]
+    # what the last timed step computed: the correctness gate on this rank's shard (ground truth of the
+    # seeded fault mix) and, with --dump-outputs, the arrays written out
+    host = out.to_host()
+    flags_ok = bool(np.array_equal(host.grant_flags, synth.expected_flags))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, host, gathered.cpu().numpy().view(np.uint32) if comm is not None else None)
     t_max, wall_max, all_ok, total_grants_verified = reduce_over_ranks(dist, ev_s, wall, flags_ok, N, "cuda")
     value = total_grants_verified * args.steps / t_max
 
@@ -414,7 +459,6 @@ def main():
             cpu = None
         if os.path.exists(batch_file):
             os.remove(batch_file)
-        extras = world == 1 and not args.headline_only  # side measurements: single-GPU runs only
         shard_leg = None
         if world == 1 and (args.shard_sizes or (extras and not args.no_shard_sizes)):
             shard_leg = shard_sizes_leg(args, ver, synth, C_total, R, strict, local_rank, stream, stage_ms[2])
@@ -479,7 +523,7 @@ def main():
             "cluster_c5_proxy": cluster,
             "wall_s": round(wall_max, 4),
             "correct_vs_ground_truth": all_ok,
-            "prep_dedup": prep_dedup(batch) if rank == 0 else None,
+            "prep_dedup": prep_dedup(batch) if args.full else None,
         }
         result["summary"] = summary(result, stage_ms, t_max / args.steps * 1e3)
     if dist is not None:

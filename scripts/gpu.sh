@@ -7,7 +7,7 @@
 #   tests        every -m gpu test (TESTS= to narrow, e.g. TESTS=tests/test_gpu_parity.py)
 #   parity       the quick parity subset for the in-tree lib and each of $AB_LIBS
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench (C4 headline + every leg) -> gpurun_out/bench.json
+#   bench        the full bench (bench.py --full: C4 headline + every leg) -> $OUT/bench.json
 #   ab           headline-only bench, in-tree lib vs each of $AB_LIBS, alternated twice
 #                (AB_ENV="A=... B=..." per-variant env overrides are not supported: use libs)
 #   abenv        headline-only bench, default env vs each ';'-separated env setting of
@@ -43,7 +43,7 @@ for step in "$@"; do
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || fail smoke $OUT/smoke.log
     tail -1 $OUT/smoke.log ;;
   bench)
-    timeout -k 10 ${BENCH_TIMEOUT:-900} python -u bench.py --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
+    timeout -k 10 ${BENCH_TIMEOUT:-900} python -u bench.py --full --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
     python -c "import json;d=json.load(open('$OUT/bench.json'));print(round(d['value']/1e6,2),'M grants/s', d.get('stage_ms'), d['roofline']['frac'])" ;;
   ab)
     for i in 1 2; do
