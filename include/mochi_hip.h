@@ -252,7 +252,10 @@ int mochi_verify_batch_device(mochi_ctx* ctx, const mochi_batch* batch, const mo
 /*
  * The raw RSA public operation y = s^65537 mod n for n signatures (big-endian,
  * 256 bytes each) under key `signer[i]`, on the device, through the same
- * kernels as the verify path (k_rsa_pow + k_rsa_final).  out_be: n * 256
+ * bucketing and squaring-chain kernels as the verify path, then k_rsa_raw.
+ * The call follows the context's small-batch setting as the verify calls do
+ * (mochi_ctx_set_small_batch): up to that many signatures run k_bucket_small
+ * + k_rsa_pow_lat, more run the bucket kernels + k_rsa_pow.  out_be: n * 256
  * bytes.  out_z (optional, n * 74 words): the squaring-chain intermediate
  * z = s^(2^16) mod n in radix-2^28 limbs, not fully reduced (< 2^2064), for
  * tests.  Host memory, synchronous.

@@ -1743,6 +1743,10 @@ int mochi_rsa_public_op(mochi_ctx* c, uint32_t n, const uint8_t* sig_be, const u
   a.xbuf = c->xbuf.as<uint32_t>();
   a.dbg_y = c->dev_out.as<uint32_t>();
   a.skip_prep_tally = true;
+  // the context's small-batch setting picks the launch sequence as in the verify
+  // calls (k_bucket_small + k_rsa_pow_lat); prep stays off, so k_bucket_small
+  // never reads the zeroed PrepArgs, and dbg_y keeps the final on k_rsa_raw
+  a.small_grants = c->small_grants;
   std::vector<uint32_t> y(64 * (size_t)n), perm, z;
   bool ok = hipMemcpyAsync(din, sig_be, sig_bytes, hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemcpyAsync(dsigner, signer, sizeof(uint16_t) * n, hipMemcpyHostToDevice, st) == hipSuccess &&

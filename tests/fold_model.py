@@ -21,9 +21,11 @@ mochi_fold_matrix and against pow() in tests/test_fold_cpu.py.
 # int32 whose low three bytes are biased (XOR 0x80) and whose top byte is a
 # signed digit, and cadd carries 128 * sum_{j, b<3} R_{j,b} + 2401 n (the
 # multiple of n keeps x' > 0 whatever the signs).
+import operator
+
 import numpy as np
 
-L = 74          # limbs of x (2072 bits)
+L = 74         # limbs of x (2072 bits)
 F = 73          # fold point: t_lo = limbs [0, 73)
 NH = 75         # t_hi limbs 73..147
 KSTEPS = 10     # 8 limbs (32 bytes) per K-step, 80 limb slots >= 75
@@ -85,22 +87,25 @@ def _columns(a, b, sqr):
     once and doubled when sqr), normalised through the kernel's 64-bit carry chain."""
     na = len(a)
     out, carry = [], 0
+    if sqr:
+        # kara_dev.h half_square: the lower index of every cross product is
+        # read doubled (a_i is doubled in place after column 2i), the square
+        # term joins the chain; every operand fits 32 bits, every partial
+        # sum 64 bits (the chain only grows, so the final check covers it)
+        a = [int(v) for v in a]
+        d = [2 * v for v in a]
+        assert all(0 <= v < 1 << 32 for v in d)
+    else:
+        a, b = [int(v) for v in a], [int(v) for v in b]
     for k in range(2 * na - 1):
         lo, hi = max(0, k - na + 1), min(k, na - 1)
         if sqr:
-            # kara_dev.h half_square: the lower index of every cross product is
-            # read doubled (a_i is doubled in place after column 2i), the square
-            # term joins the chain; every operand fits 32 bits, every partial
-            # sum 64 bits (the chain only grows, so the final check covers it)
-            acc = carry
-            for i in range(lo, (k - 1) // 2 + 1):
-                if i < k - i:
-                    assert 2 * a[i] < 1 << 32 and a[k - i] < 1 << 32
-                    acc += (2 * a[i]) * a[k - i]
+            m = (k - 1) // 2 + 1  # cross products (2 a_i) a_(k-i), lo <= i < m (so i < k - i)
+            acc = carry + (sum(map(operator.mul, d[lo:m], a[k - lo:k - m:-1])) if m > lo else 0)
             if k % 2 == 0:
                 acc += a[k // 2] * a[k // 2]
         else:
-            acc = carry + sum(a[i] * b[k - i] for i in range(lo, hi + 1))
+            acc = carry + sum(map(operator.mul, a[lo:hi + 1], b[k - lo::-1] if hi == k else b[k - lo:k - hi - 1:-1]))
         assert acc < 1 << 64, "column sum overflows the 64-bit accumulator"
         out.append(acc & M28)
         carry = acc >> 28
@@ -155,13 +160,11 @@ def kara_terms(a, b=None):
 def fold_signed(t, W, cadd, sub_h=None):
     """x' = t_lo + fold(t_hi) + cadd (- h): the kernel's fold of signed limbs."""
     t_lo, t_hi = t[:F], t[F:]
-    kb = []
-    for j in range(NH):
-        v = t_hi[j] & 0xFFFFFFFF
-        for bb in range(4):
-            byte = (v >> (8 * bb)) & 0xFF
-            kb.append(byte - 128 if bb < 3 else (byte - 256 if byte >= 128 else byte))
-    c = (W @ np.array(kb, np.int64)).reshape(L, 4)
+    # each int32 limb's bytes: 0..2 biased by -128, byte 3 read as a signed digit
+    kb = np.array([v & 0xFFFFFFFF for v in t_hi], "<u4").view(np.uint8).astype(np.int64).reshape(NH, 4)
+    kb[:, :3] -= 128
+    kb[:, 3] -= 256 * (kb[:, 3] >= 128)
+    c = (W @ kb.reshape(-1)).reshape(L, 4)
     assert np.abs(c).max() < 2 ** 31
     out, carry = [], 0
     for q in range(L):

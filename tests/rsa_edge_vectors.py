@@ -1,0 +1,321 @@
+"""Test infrastructure: forged near-miss signatures and structured operands for the
+RSA kernels (k_rsa_pow / k_rsa_pow_lat, k_rsa_final / k_rsa_final_lat, k_rsa_raw).
+
+Pure Python, no GPU, no crypto module.  The committed test keys are private keys,
+so for any target y in [0, n) the signature s = y^d mod n has s^65537 mod n == y
+exactly: the final check can be handed a value that differs from the expected
+encoding EM in one chosen limb, bit or byte.  Exactly one target per message is
+valid, y == EM; that is the ground truth by construction (OpenSSL, through the
+oracle, is the second opinion: tests/test_rsa_edge_vectors_cpu.py).
+
+Signing costs two 1024-bit modular powers in Python (about 10 ms), so the sets
+are sized per key: the full limb and encoding sets for server key 0, the 73
+limb-boundary flips for the other server keys, EM +- 2^(28k) for the edge keys
+(tests/golden/edge_moduli.json), built once per process.
+"""
+from __future__ import annotations
+
+import base64
+import functools
+import hashlib
+import json
+import os
+from dataclasses import dataclass
+from typing import List, Tuple
+
+import fold_model as FM
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden")
+E = 65537
+B, L = 28, 74
+M28 = (1 << B) - 1
+# the constants of tests/test_final_algebra.py (EMSA-PKCS1-v1_5, SHA-256)
+DIGEST_INFO = bytes.fromhex("3031300d060960864801650304020105000420")
+PAD_BYTES = 202
+CPAD = int.from_bytes(b"\x00\x01" + b"\xff" * PAD_BYTES + b"\x00" + DIGEST_INFO + b"\x00" * 32, "big")
+XMAX = 1 << 2064
+
+# moduli nobody can sign under: they take part in the residue checks only
+NON_RSA_MODULI = {"all_ones": (1 << 2048) - 1, "two_2047_plus_1": (1 << 2047) | 1}
+
+
+# ---------------------------------------------------------------------------
+# keys
+# ---------------------------------------------------------------------------
+def _der(buf: bytes, pos: int) -> Tuple[int, int, int]:
+    """(tag, start, end) of the DER element at pos."""
+    tag, ln = buf[pos], buf[pos + 1]
+    pos += 2
+    if ln & 0x80:
+        k = ln & 0x7F
+        ln = int.from_bytes(buf[pos:pos + k], "big")
+        pos += k
+    assert pos + ln <= len(buf)
+    return tag, pos, pos + ln
+
+
+def _der_ints(buf: bytes, pos: int, end: int) -> List[int]:
+    out = []
+    while pos < end:
+        tag, a, b = _der(buf, pos)
+        assert tag == 0x02
+        out.append(int.from_bytes(buf[a:b], "big"))
+        pos = b
+    return out
+
+
+def rsa_private(pem: bytes):
+    """(n, e, d, p, q, dp, dq, qinv) of an unencrypted PKCS#8 RSA private key: a minimal
+    DER walk -- PrivateKeyInfo { 0, AlgorithmIdentifier, OCTET STRING { RSAPrivateKey } }."""
+    body = b"".join(ln for ln in pem.strip().splitlines() if not ln.startswith(b"-----"))
+    der = base64.b64decode(body)
+    tag, a, end = _der(der, 0)
+    assert tag == 0x30 and end == len(der)
+    tag, a, b = _der(der, a)          # version
+    assert tag == 0x02 and der[a:b] == b"\x00"
+    tag, a, b = _der(der, b)          # AlgorithmIdentifier: rsaEncryption
+    assert tag == 0x30 and bytes.fromhex("06092a864886f70d010101") in der[a:b]
+    tag, a, b = _der(der, b)          # privateKey
+    assert tag == 0x04
+    tag, a, b = _der(der, a)          # RSAPrivateKey
+    assert tag == 0x30
+    ver, n, e, d, p, q, dp, dq, qinv = _der_ints(der, a, b)[:9]
+    assert ver == 0 and p * q == n and pow(pow(2, e, n), d, n) == 2
+    assert dp == d % (p - 1) and dq == d % (q - 1) and qinv * q % p == 1
+    return n, e, d, p, q, dp, dq, qinv
+
+
+@dataclass(frozen=True)
+class Key:
+    name: str
+    n: int
+    d: int
+    p: int
+    q: int
+    dp: int
+    dq: int
+    qinv: int
+
+    @property
+    def modulus_be(self) -> bytes:
+        return self.n.to_bytes(256, "big")
+
+    def raw_sign(self, y: int) -> int:
+        """y^d mod n by the CRT."""
+        assert 0 <= y < self.n
+        m1, m2 = pow(y % self.p, self.dp, self.p), pow(y % self.q, self.dq, self.q)
+        return m2 + (self.qinv * (m1 - m2) % self.p) * self.q
+
+
+def server_pem(i: int) -> bytes:
+    with open(os.path.join(GOLDEN, "keys", f"server{i}.pem"), "rb") as f:
+        return f.read()
+
+
+@functools.lru_cache(maxsize=None)
+def server_key(i: int) -> Key:
+    n, e, d, p, q, dp, dq, qinv = rsa_private(server_pem(i))
+    assert e == E
+    return Key(f"server{i}", n, d, p, q, dp, dq, qinv)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_keys() -> Tuple[Key, ...]:
+    """The constructed keys of tests/golden/edge_moduli.json, in the file's order."""
+    with open(os.path.join(GOLDEN, "edge_moduli.json")) as f:
+        doc = json.load(f)
+    assert doc["e"] == E
+    out = []
+    for name, pq in doc["keys"].items():
+        p, q = int(pq["p"], 16), int(pq["q"], 16)
+        n = p * q
+        assert n & 1 and n.bit_length() == 2048, name
+        d = pow(E, -1, (p - 1) * (q - 1))
+        assert pow(pow(2, E, n), d, n) == 2
+        out.append(Key(name, n, d, p, q, d % (p - 1), d % (q - 1), pow(q, -1, p)))
+    return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# encoding and targets
+# ---------------------------------------------------------------------------
+def grant_message(tag: str) -> bytes:
+    """A well-formed Grant (objectId, timestamp 1000, a 128-character transactionHash)."""
+    oid = f"EDGE_VECTOR_{tag}".encode()
+    th = hashlib.sha512(f"edge-{tag}".encode()).hexdigest().encode()
+    assert len(oid) < 128 and len(th) == 128
+    return b"\x0a" + bytes([len(oid)]) + oid + b"\x10\xe8\x07" + b"\x22\x80\x01" + th
+
+
+def digest_int(msg: bytes) -> int:
+    return int.from_bytes(hashlib.sha256(msg).digest(), "big")
+
+
+def em(msg: bytes) -> int:
+    """The EMSA-PKCS1-v1_5 encoding of msg as an integer: 00 01 FF*202 00 DigestInfo H."""
+    return CPAD + digest_int(msg)
+
+
+def _in_range(n, items):
+    seen, out = set(), []
+    for name, y in items:
+        if 0 <= y < n and y not in seen:
+            seen.add(y)
+            out.append((name, y))
+    return out
+
+
+def last_carry_targets(n: int, EM: int):
+    """EM -+ 2^2072 (mod n).  EM +- 2^(28k) moves the final check's D' by 2^(28(k-1)), so
+    k <= 73 reaches compare positions 0..72 only; position 73 -- the last carry
+    against n's top limb -- takes 2^(28*74), which exists only reduced mod n.  The
+    minus sign leaves D' = n - 2^(28*73) for every representative of the fold.
+    EM - 2^(28*73) is negative as well (EM < 2^2033) and joins them reduced: D' =
+    n - 2^(28*72), the one clean change of position 72 when that limb of n is all ones."""
+    return [("last_carry-", (EM - (1 << (B * L))) % n), ("last_carry+", (EM + (1 << (B * L))) % n),
+            (f"minus_2^{B * (L - 1)}_wrapped", (EM - (1 << (B * (L - 1)))) % n)]
+
+
+def flip_set(n: int, EM: int):
+    """EM with bit 28j flipped, j = 1..73, and the last-carry targets."""
+    return _in_range(n, [(f"flip_b{B * j}", EM ^ (1 << (B * j))) for j in range(1, L)] + last_carry_targets(n, EM))
+
+
+def plus_minus_set(n: int, EM: int):
+    """EM +- 2^(28k), k = 1..73 (the flips of flip_set among them), and the last-carry targets."""
+    items = []
+    for k in range(1, L):
+        items += [(f"plus_2^{B * k}", EM + (1 << (B * k))), (f"minus_2^{B * k}", EM - (1 << (B * k)))]
+    return _in_range(n, items + last_carry_targets(n, EM))
+
+
+def limb_set(n: int, EM: int):
+    """Targets one limb, one bit or one carry ripple away from EM, and the trivial residues."""
+    items = []
+    for j in range(1, L):
+        items += [(f"flip_b{B * j}", EM ^ (1 << (B * j))), (f"flip_b{B * j - 1}", EM ^ (1 << (B * j - 1)))]
+    for k in range(L):  # carries / borrows rippling through the FF padding
+        items += [(f"plus_2^{B * k}", EM + (1 << (B * k))), (f"minus_2^{B * k}", EM - (1 << (B * k)))]
+    items += [("zero", 0), ("one", 1), ("n-1", n - 1), ("n-EM", n - EM)]
+    return _in_range(n, items + last_carry_targets(n, EM))
+
+
+def encoding_set(n: int, EM: int):
+    """EM with one bit flipped per structural byte of the encoding and across the digest."""
+    def byte_bit(i, b):  # bit b of big-endian byte i of the 256-byte encoding
+        return 8 * (255 - i) + b
+
+    bits = [("lead00_b0", byte_bit(0, 0)), ("lead00_b6", byte_bit(0, 6)), ("lead00_b7", byte_bit(0, 7)),
+            ("bt01_b0", byte_bit(1, 0)), ("bt01_b1", byte_bit(1, 1)),
+            ("ps_first", byte_bit(2, 7)), ("ps_middle", byte_bit(2 + PAD_BYTES // 2, 3)),
+            ("ps_last", byte_bit(1 + PAD_BYTES, 0)), ("sep00", byte_bit(2 + PAD_BYTES, 0))]
+    for i in range(len(DIGEST_INFO)):
+        bits.append((f"digestinfo{i}", byte_bit(3 + PAD_BYTES + i, i % 8)))
+    dig = set(range(0, 256, 8)) | {0, 1, 254, 255}
+    for w in range(1, 8):
+        dig |= {32 * w - 2, 32 * w - 1, 32 * w, 32 * w + 1}
+    bits += [(f"digest_b{b}", b) for b in sorted(dig)]
+    return _in_range(n, [(name, EM ^ (1 << b)) for name, b in bits])
+
+
+def structured_operands(n: int):
+    """Signature values s (< 2^2048) whose limbs are structured: the first squaring of
+    the chain and the final product z*s are where the structure reaches the product
+    code.  Values >= n still run the chain (only z is checked for them)."""
+    H = FM.HALF
+    top = (1 << 2048) - 1
+    lo_ones = (1 << (B * H)) - 1
+    hi_bits = 2048 - B * H  # x_hi holds 1012 bits of a 2048-bit value
+    v = int.from_bytes(hashlib.sha512(b"structured operand").digest() * 2, "big") >> (1024 - hi_bits)
+    alt = sum(M28 << (B * j) for j in range(0, L, 2))
+    items = [("lo_ones_hi_zero", lo_ones), ("lo_zero_hi_ones", top - lo_ones),
+             ("lo_eq_hi_ones", ((1 << hi_bits) - 1) * ((1 << (B * H)) + 1)), ("lo_eq_hi", v * ((1 << (B * H)) + 1)),
+             ("alternate_even", alt & top), ("alternate_odd", (alt << B) & top)]
+    for j in range(L):
+        items += [(f"2^{B * j}", 1 << (B * j)), (f"ones<<{B * j}", (M28 << (B * j)) & top)]
+    items += [("2^1022", 1 << 1022), ("2^1022-1", (1 << 1022) - 1), ("zero", 0), ("one", 1), ("two", 2),
+              ("n-1", n - 1), ("n-2", n - 2), ("(n-1)/2", (n - 1) // 2), ("(n+1)/2", (n + 1) // 2), ("2^2048-1", top)]
+    return _in_range(1 << 2048, items)
+
+
+# ---------------------------------------------------------------------------
+# signed vectors
+# ---------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Vector:
+    name: str
+    y: int          # the target: sig^65537 mod n
+    sig: bytes      # 256 bytes, big-endian
+    valid: bool     # y == EM
+
+
+@dataclass(frozen=True)
+class KeyVectors:
+    key: Key
+    msg: bytes
+    vectors: Tuple[Vector, ...]
+
+
+def sign_targets(key: Key, msg: bytes, targets) -> KeyVectors:
+    """The valid signature first, then one forged signature per target."""
+    EM = em(msg)
+    assert EM < key.n
+    out = [Vector("valid", EM, key.raw_sign(EM).to_bytes(256, "big"), True)]
+    for name, y in targets:
+        if y != EM:
+            out.append(Vector(name, y, key.raw_sign(y).to_bytes(256, "big"), False))
+    return KeyVectors(key, msg, tuple(out))
+
+
+@functools.lru_cache(maxsize=None)
+def server_vectors() -> Tuple[KeyVectors, ...]:
+    """Server key 0: the full limb and encoding sets.  Keys 1..6: the limb-boundary flips."""
+    out = []
+    for i in range(7):
+        key, msg = server_key(i), grant_message(f"server{i}")
+        EM = em(msg)
+        targets = limb_set(key.n, EM) + encoding_set(key.n, EM) if i == 0 else flip_set(key.n, EM)
+        out.append(sign_targets(key, msg, _in_range(key.n, targets)))
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_vectors() -> Tuple[KeyVectors, ...]:
+    """The five edge keys: EM +- 2^(28k) -- under an all-ones or an all-zeros limb of n one
+    sign ripples through the final compare and the other stays in its limb."""
+    out = []
+    for key in edge_keys():
+        msg = grant_message(key.name)
+        out.append(sign_targets(key, msg, plus_minus_set(key.n, em(msg))))
+    return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# the fold model's squaring chain over the structured operands
+# ---------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def model_weights(n: int):
+    _, cadd, W = FM.make_weights(n)
+    return W, cadd
+
+
+@functools.lru_cache(maxsize=None)
+def chain_moduli() -> Tuple[Tuple[str, int], ...]:
+    """The seven moduli of the residue checks: the edge keys' and the two non-RSA ones."""
+    return tuple((k.name, k.n) for k in edge_keys()) + tuple(NON_RSA_MODULI.items())
+
+
+@functools.lru_cache(maxsize=None)
+def model_chain(n: int):
+    """[(name, s, z limbs)]: 16 fold_square steps of the model from every structured
+    operand, every one of the model's own assertions (64-bit columns, |t_j| < 2^29,
+    int32 halves, no carry out of limb 73) checked on the way."""
+    W, cadd = model_weights(n)
+    out = []
+    for name, s in structured_operands(n):
+        x = FM.to_limbs(s)
+        for _ in range(16):
+            x = FM.fold_square(x, W, cadd)
+        out.append((name, s, tuple(x)))
+    return tuple(out)

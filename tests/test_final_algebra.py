@@ -31,8 +31,10 @@ def limbs(v, n=L):
     return [(v >> (B * j)) & MASK for j in range(n)]
 
 
-def final_check(n, s, x_rep, h_int):
-    """Limb-exact replay of k_rsa_final after the fold (x given)."""
+def final_diffs(n, x_rep, h_int):
+    """Limb-exact replay of k_rsa_final after the fold (x given): what each of the 74
+    compare positions contributes to `diff` -- D' limb k against n's limb k for
+    k = 0..72, then the last carry against n's top limb."""
     n0inv = (-pow(n, -1, 1 << B)) % (1 << B)
     D = x_rep + (n - CPAD) - h_int
     assert 0 < D < XMAX + n
@@ -40,16 +42,24 @@ def final_check(n, s, x_rep, h_int):
     m = ((Dl[0] * n0inv) & 0xFFFFFFFF) & MASK
     acc = m * N[0] + Dl[0]
     assert acc & MASK == 0 and acc < 1 << 64
-    c, diff = acc >> B, 0
+    c, diffs = acc >> B, []
     for k in range(1, L):
         acc = m * N[k] + Dl[k] + c
         assert acc < 1 << 64
-        diff |= (acc & MASK) ^ N[k - 1]
+        diffs.append((acc & MASK) ^ N[k - 1])
         c = acc >> B
-    diff |= int(c != N[L - 1])
+    diffs.append(int(c != N[L - 1]))
     # the bound the kernel relies on: D' in (0, 2n)
     Dp = (D + m * n) >> B
     assert 0 < Dp < 2 * n
+    return diffs
+
+
+def final_check(n, s, x_rep, h_int):
+    """The kernel's verdict: s < n and no compare position differs."""
+    diff = 0
+    for v in final_diffs(n, x_rep, h_int):
+        diff |= v
     return s < n and diff == 0
 
 

@@ -62,10 +62,15 @@ def assert_same(g: mh.Verdicts, o: mh.Verdicts, what=""):
             np.testing.assert_array_equal(getattr(g, k), getattr(o, k), err_msg=f"{k} {what}")
 
 
-def test_rsa_public_op_matches_python_pow():
+@pytest.mark.parametrize("seq", ["large", "default"])
+def test_rsa_public_op_matches_python_pow(seq):
+    """`large`: set_small_batch(0), the bucket kernels + k_rsa_pow; `default`: these
+    300 signatures take the small-batch sequence (k_bucket_small + k_rsa_pow_lat)."""
     pems = W.load_keys(3)
     mods = [O.pem_modulus(p) for p in pems]
     ver = mh.Verifier(mods, 0)
+    if seq == "large":
+        ver.set_small_batch(0)
     rng = np.random.default_rng(7)
     sigs, signer = [], []
     for i in range(300):
@@ -548,7 +553,7 @@ def test_grant_dedup_one_byte_differences(pool4, ver4, shared_first, small):
                 "g0_hash": [hmis, base, base, base], "oid_flip": [base, base, base, oflip],
                 "longer": [base, longer, base, base], "all_skew": [base, skew, skew, skew]}
     certs = []
-    for _ in range(40):  # enough certificates for several waves of k_grant_dedup lanes
+    for _ in range(40):  # enough certificates for several waves of k_grant_prep_cert lanes
         for gs in variants.values():
             certs.append([(gb, r, 0) for r, gb in enumerate(gs)])
     # two key slots in one certificate (k = 2), interleaved
