@@ -1,5 +1,9 @@
 """Producer-side signing on the device (k_rsa_sign, CRT): every signature is
-byte-identical to OpenSSL's (PKCS#1 v1.5 is deterministic) and verifies."""
+byte-identical to OpenSSL's (PKCS#1 v1.5 is deterministic) and verifies.
+
+The server keys and random grants here; constructed keys (structured primes, short
+CRT exponents, both prime orders), batch-size edges and the SHA-256 length and
+alignment sweep: tests/test_sign_edges_gpu.py."""
 import numpy as np
 import pytest
 
