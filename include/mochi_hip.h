@@ -491,6 +491,82 @@ int mochi_write2_decode(mochi_ctx* ctx, const mochi_write2_batch* batch, mochi_w
 void mochi_write2_decoded_free(mochi_write2_decoded* d);
 
 /* ------------------------------------------------------------------------
+ * Write2ToServer ENCODE: the inverse of the decoder above, the client's
+ * certificate assembly (MochiDBClient.java:333-338).  An SoA batch of the
+ * MultiGrants a client collected becomes the Write2ToServer bodies, one blob
+ * with msg_off / msg_len, laid out as mochi_write2_batch takes them, byte for
+ * byte what protobuf-java writes (MochiProtocol.proto:107-147): fields in
+ * number order, every map entry with its key and its value, proto3 defaults
+ * omitted, MultiGrant.hash never written.  The key of a grants-map entry and of
+ * its grantSignatures entry is the grant's objectId, read from the grant's own
+ * bytes; grant bytes are copied as given.  The caller lists MultiGrants and
+ * grants in the order it wants on the wire.
+ * ------------------------------------------------------------------------ */
+typedef struct mochi_write2_source {
+  uint32_t n_msgs, n_mgs, n_grants, n_ops;
+  const uint8_t*  grant_bytes;  uint64_t grant_bytes_len;
+  const uint64_t* grant_off;    /* [N] any alignment                              */
+  const uint32_t* grant_len;    /* [N]                                            */
+  const uint8_t*  sig;          /* [N*256] or NULL = no grantSignatures entries   */
+  const uint32_t* cert_mg_off;  /* [M+1]  MultiGrants per message, wire order     */
+  const uint32_t* mg_grant_off; /* [n_mgs+1] grants per MultiGrant, map order     */
+  const uint16_t* mg_signer;    /* [n_mgs] key index: MultiGrant.serverId AND the
+                                   certificate map key = that key's server id     */
+  const uint8_t*  strings;      uint64_t strings_len;  /* operands and client ids */
+  const uint32_t* cert_op_off;  /* [M+1] */
+  const uint8_t*  op_action;    /* [O] OperationAction value (0 omitted)          */
+  const uint64_t* op1_off; const uint32_t* op1_len;   /* [O] operand1 (0 = omitted) */
+  const uint64_t* op2_off; const uint32_t* op2_len;   /* [O] or both NULL          */
+  const uint64_t* client_off; const uint32_t* client_len; /* [M] MultiGrant.clientId of
+                                   every MultiGrant of message m; both NULL = empty */
+} mochi_write2_source;
+
+/* Per-message encode status.  A message with a status other than OK is emitted
+ * with length 0; the call still succeeds.  With several causes the lowest
+ * value is reported. */
+enum mochi_enc_status {
+  MOCHI_ENC_OK = 0,
+  MOCHI_ENC_BAD_GRANT = 1,  /* a grant does not parse (or lies outside grant_bytes) */
+  MOCHI_ENC_BAD_SIGNER = 2, /* an mg_signer outside the id table                    */
+  MOCHI_ENC_TOO_LONG = 3,   /* the message would be 2^31 bytes or more              */
+};
+
+/* A safe upper bound on the wire size, from the counts and the two blob
+ * lengths of `counts_only` alone (no pointer is dereferenced).  Grants may
+ * share bytes, so every grant is taken at grant_bytes_len and every string at
+ * strings_len, capped by 2^31 - 1 bytes per message: safe, not tight.  A caller
+ * that wants the exact size calls the encoder with wire_cap = 0 and reads
+ * *wire_len. */
+uint64_t mochi_write2_encode_bound(const mochi_write2_source* counts_only, uint32_t max_id_len);
+
+/* Host form: every array in host memory, no context, no GPU (the CPU twin of
+ * the device form, as mochi_write1_classify is).  ids / id_off[n_ids+1] is the
+ * server-id table (as mochi_ctx_set_server_ids takes it).  Messages are packed
+ * back to back: msg_off[m] is the sum of the earlier lengths (64-bit).
+ * msg_off[M], msg_len[M] and status[M] are always written; when wire_cap is
+ * smaller than the total the call returns MOCHI_EINVAL with *wire_len = the
+ * size needed and writes no byte of `wire`.  Inconsistent CSR arrays or a
+ * string slice outside `strings` are MOCHI_EINVAL. */
+int mochi_write2_encode(const mochi_write2_source* src, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids,
+                        uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len, uint8_t* status,
+                        uint64_t* wire_len);
+
+/* Device form: every array of `src` and wire / msg_off / msg_len / status in
+ * DEVICE memory, wire_len on the host; server ids from mochi_ctx_set_server_ids
+ * (MOCHI_EINVAL without them).  The call waits for the total size, then returns
+ * with the emit kernels enqueued on `stream` (hipStream_t; NULL = null stream).
+ * Same bytes, offsets, statuses and capacity rule as the host form; the CSR
+ * arrays and string slices are trusted. */
+int mochi_write2_encode_device(mochi_ctx* ctx, const mochi_write2_source* src, uint8_t* wire, uint64_t wire_cap,
+                               uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                               void* stream);
+/* Per-kernel device time (ms) of the last mochi_write2_encode_device call made
+ * while profiling was on (mochi_ctx_set_profiling): [0] k_enc_mg, [1] k_enc_msg,
+ * [2] the 64-bit scan, [3] k_enc_hdr_mg, [4] k_enc_hdr_msg, [5] k_enc_copy.
+ * Waits for that call.  n_kernels <= 6. */
+int mochi_ctx_read_encode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n_kernels);
+
+/* ------------------------------------------------------------------------
  * Producer side on the device: SHA256withRSA over each grant's bytes with ONE
  * server's private key (RSA-2048, CRT), the Write1 signing site
  * (InMemoryDataStore.java:283-295, MochiProtocol.proto:123 TODO).  Output is

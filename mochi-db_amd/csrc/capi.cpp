@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "mont.h"
 #include "w2.h"
+#include "w2_encode.h"
 #include "w2_host.h"
 
 namespace {
@@ -315,6 +316,11 @@ struct mochi_ctx {
       w2_mgo, w2_ots, w2_okoff, w2_oklen, w2_same;
   PinnedBuf w2_tot;
   hipEvent_t ev_tot = nullptr;
+  // Write2 encoder (w2_encode.hip): per-batch scratch, scan temp, the wire size on the host
+  DevBuf w2e_scratch, w2e_scan;
+  PinnedBuf w2e_tot;
+  std::vector<hipEvent_t> w2e_ev;  // per-kernel events of the last encode call made while profiling
+  bool w2e_ev_valid = false;
   // the last host-path call's certificate accept bitmap on the device (a slice
   // of dev_out, valid until the next call on this context; nullptr when the
   // device copy is not the final verdict, e.g. after host fallback decisions):
@@ -491,6 +497,7 @@ void mochi::ctx_free(mochi_ctx* c) {
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
   if (c->ev_tot) (void)hipEventDestroy(c->ev_tot);
+  for (auto e : c->w2e_ev) (void)hipEventDestroy(e);
   if (c->s_out) (void)hipStreamDestroy(c->s_out);
   if (c->d_keys) (void)hipFree(c->d_keys);
   if (c->d_fold) (void)hipFree(c->d_fold);
@@ -1275,6 +1282,122 @@ void mochi_write2_decoded_free(mochi_write2_decoded* d) {
   memset(d, 0, sizeof *d);
 }
 
+// ---- Write2 encode (client certificate assembly) ----------------------------
+
+namespace {
+
+int check_write2_source(const mochi_write2_source* s, const uint64_t* msg_off, const uint32_t* msg_len,
+                        const uint8_t* status, const uint64_t* wire_len) {
+  if (!s || !wire_len) return fail(MOCHI_EINVAL, "null argument");
+  if (s->n_msgs && (!msg_off || !msg_len || !status)) return fail(MOCHI_EINVAL, "msg_off / msg_len / status required");
+  if (!s->cert_mg_off || !s->mg_grant_off || !s->cert_op_off)
+    return fail(MOCHI_EINVAL, "cert_mg_off / mg_grant_off / cert_op_off required");
+  if (s->n_mgs && !s->mg_signer) return fail(MOCHI_EINVAL, "mg_signer required");
+  if (s->n_grants && (!s->grant_off || !s->grant_len || (!s->grant_bytes && s->grant_bytes_len)))
+    return fail(MOCHI_EINVAL, "grant_bytes / grant_off / grant_len required");
+  if (s->n_ops && (!s->op_action || !s->op1_off || !s->op1_len)) return fail(MOCHI_EINVAL, "op_action / op1_off / op1_len required");
+  if (!s->op2_off != !s->op2_len) return fail(MOCHI_EINVAL, "op2_off and op2_len go together");
+  if (!s->client_off != !s->client_len) return fail(MOCHI_EINVAL, "client_off and client_len go together");
+  if (s->n_msgs == 0xFFFFFFFFu) return fail(MOCHI_EINVAL, "batch too large");
+  return MOCHI_OK;
+}
+
+int run_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8_t* wire, uint64_t wire_cap,
+                             uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                             hipStream_t st) {
+  if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
+  *wire_len = 0;
+  if (s->n_msgs == 0) return MOCHI_OK;
+  int rc;
+  size_t scan_bytes = 0;
+  if (!mochi::w2_small(s->n_msgs)) HIP_TRY(mochi::w2_enc_scan_temp_bytes(s->n_msgs + 1, &scan_bytes));
+  if ((rc = c->w2e_scratch.ensure(mochi::w2_enc_scratch_bytes(s->n_msgs, s->n_mgs, s->n_grants))) ||
+      (rc = c->w2e_scan.ensure(scan_bytes)) || (rc = c->w2e_tot.ensure(8)))
+    return rc;
+  mochi::W2EncArgs a;
+  memset(&a, 0, sizeof a);
+  a.src = *s;
+  a.ids = c->ids.as<uint8_t>();
+  a.id_off = c->id_off.as<uint32_t>();
+  a.n_ids = c->n_ids;
+  a.wire = wire;
+  a.msg_off = msg_off;
+  a.msg_len = msg_len;
+  a.status = status;
+  a.scan_temp = c->w2e_scan.p;
+  a.scan_temp_bytes = c->w2e_scan.cap;
+  mochi::w2_enc_carve(a, c->w2e_scratch.p);
+  c->w2e_ev_valid = false;
+  if (c->profiling) {
+    while (c->w2e_ev.size() < (size_t)mochi::kW2EncEvents) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      c->w2e_ev.push_back(e);
+    }
+    a.ev = c->w2e_ev.data();
+  }
+  HIP_TRY(scratch_acquire(c, st));
+  HIP_TRY(mochi::launch_w2_enc_size(a, st));
+  uint64_t* tot = (uint64_t*)c->w2e_tot.p;
+  HIP_TRY(hipMemcpyAsync(tot, a.off64 + s->n_msgs, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(c->ev_tot, st));
+  HIP_TRY(hipEventSynchronize(c->ev_tot));
+  *wire_len = *tot;
+  if (*tot <= wire_cap) HIP_TRY(mochi::launch_w2_enc_emit(a, st));
+  c->w2e_ev_valid = a.ev && *tot <= wire_cap;
+  HIP_TRY(scratch_release(c, st));
+  if (*tot > wire_cap)
+    return fail(MOCHI_EINVAL, "wire_cap (%llu) is smaller than the encoded size (%llu)", (unsigned long long)wire_cap,
+                (unsigned long long)*tot);
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+uint64_t mochi_write2_encode_bound(const mochi_write2_source* s, uint32_t max_id_len) {
+  if (!s) return 0;
+  // every grant at grant_bytes_len (grants may share bytes) with its objectId
+  // twice, every string at strings_len, five-byte length varints throughout
+  const unsigned __int128 gb = s->grant_bytes_len, sb = s->strings_len;
+  unsigned __int128 t = (unsigned __int128)s->n_grants * (3 * gb + MOCHI_RSA_BYTES + 40) +
+                        (unsigned __int128)s->n_mgs * (2 * (unsigned __int128)max_id_len + sb + 32) +
+                        (unsigned __int128)s->n_ops * (2 * sb + 24) + (unsigned __int128)s->n_msgs * 12;
+  const unsigned __int128 cap = (unsigned __int128)s->n_msgs * mochi::kEncMaxMsg;  // longer messages are emitted empty
+  if (t > cap) t = cap;
+  return (uint64_t)t;
+}
+
+int mochi_write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids,
+                        uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len, uint8_t* status,
+                        uint64_t* wire_len) {
+  int rc = check_write2_source(s, msg_off, msg_len, status, wire_len);
+  if (rc) return rc;
+  if (n_ids && (!ids || !id_off)) return fail(MOCHI_EINVAL, "ids / id_off required");
+  if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire required");
+  if (s->n_grants && s->grant_bytes_len && !s->grant_bytes) return fail(MOCHI_EINVAL, "grant_bytes required");
+  if (s->strings_len && !s->strings) return fail(MOCHI_EINVAL, "strings required");
+  const char* err = "";
+  rc = mochi_host::write2_encode(s, ids, id_off, n_ids, wire, wire_cap, msg_off, msg_len, status, wire_len, &err);
+  return rc ? fail(rc, "mochi_write2_encode: %s", err) : MOCHI_OK;
+}
+
+int mochi_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8_t* wire, uint64_t wire_cap,
+                               uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                               void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  int rc = check_write2_source(s, msg_off, msg_len, status, wire_len);
+  if (rc) return rc;
+  if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire required");
+  std::lock_guard<std::mutex> lk(c->mu);
+  int save = 0;
+  (void)hipGetDevice(&save);
+  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  rc = run_write2_encode_device(c, s, wire, wire_cap, msg_off, msg_len, status, wire_len, (hipStream_t)stream);
+  (void)hipSetDevice(save);
+  return rc;
+}
+
 // ---- Write2 wire path: the messages the device decoder declines -------------
 //
 // MOCHI_MSG_FALLBACK messages (repeated / merged fields, non-canonical Grant
@@ -1805,6 +1928,20 @@ int mochi_ctx_read_profile(mochi_ctx* c, float* stage_ms, uint32_t n_stages, uin
   }
   c->prof_sets.clear();
   if (n_calls) *n_calls = calls;
+  return MOCHI_OK;
+}
+
+int mochi_ctx_read_encode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n_kernels) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->w2e_ev_valid) return fail(MOCHI_EINVAL, "no encode call was made while profiling was on");
+  static const int kSpan[mochi::kW2EncStages][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}, {5, 6}, {6, 7}};
+  if (hipEventSynchronize(c->w2e_ev[mochi::kW2EncEvents - 1]) != hipSuccess)
+    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
+  for (uint32_t i = 0; i < n_kernels; i++) {
+    kernel_ms[i] = 0.f;
+    if (i < (uint32_t)mochi::kW2EncStages) (void)hipEventElapsedTime(&kernel_ms[i], c->w2e_ev[kSpan[i][0]], c->w2e_ev[kSpan[i][1]]);
+  }
   return MOCHI_OK;
 }
 

@@ -1,0 +1,450 @@
+// w2_encode.hip — Write2ToServer wire ENCODER on the device (gfx950): the
+// inverse of w2_decode.hip.  An SoA certificate batch in HBM becomes the
+// message bodies protobuf-java would write (layout: w2_encode.h), packed back
+// to back with 64-bit offsets.
+//
+// Sizes nest (a message's length varint depends on its MultiGrants', which
+// depend on their grants'), so the work goes level by level and no lane walks a
+// whole message with dependent accesses:
+//   k_enc_mg       lane = MultiGrant  parse each grant once (objectId slice kept), entry sizes
+//   k_enc_msg      lane = message     certificate / transaction / message length, status
+//   exclusive scan of the message lengths in 64 bits (hipcub; inside k_enc_msg's
+//                  single block for a small batch, where w2_small draws the line)
+//   k_enc_hdr_mg   lane = MultiGrant  every tag, length, map key, server id, client id of its entry
+//   k_enc_hdr_msg  lane = message     top-level headers and the operations
+//   k_enc_copy     16 lanes per grant the grant bytes and signatures (~90 % of the output)
+// The header kernels write the short runs between the payloads (whole dwords
+// where all four bytes are the lane's own, byte stores at a run's ends) and
+// leave the payload bytes alone; the copy kernel writes only payload bytes.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "proto_dev.h"
+#include "w2.h"
+#include "w2_encode.h"
+
+namespace mochi {
+namespace {
+
+constexpr uint64_t kNone = ~0ull;
+
+// ---- level 1: lane = MultiGrant --------------------------------------------
+__global__ __launch_bounds__(256) void k_enc_mg(mochi_write2_source s, uint32_t* __restrict__ g_oid,
+                                                uint64_t* __restrict__ mg_gpart, uint8_t* __restrict__ mg_bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s.n_mgs) return;
+  uint64_t part = 0;
+  uint32_t bad = 0;
+  const uint32_t g1 = s.mg_grant_off[i + 1];
+#pragma unroll 1
+  for (uint32_t g = s.mg_grant_off[i]; g < g1; g++) {
+    const uint64_t go = s.grant_off[g];
+    const uint32_t gl = s.grant_len[g];
+    uint32_t oo = 0, ol = 0;
+    bool ok = go <= s.grant_bytes_len && gl <= s.grant_bytes_len - go;
+    if (ok) {
+      ByteReader r;
+      r.init(s.grant_bytes + go, gl);
+      int64_t ts;
+      uint32_t ho, hl;
+      ok = parse_grant(r, ts, ho, hl, oo, ol);
+    }
+    if (!ok) {
+      bad = 1;
+      continue;
+    }
+    g_oid[2 * (size_t)g] = oo;
+    g_oid[2 * (size_t)g + 1] = ol;
+    part += enc_ld_size(enc_e1_body(ol, gl));
+    if (s.sig) part += enc_ld_size(enc_e5_body(ol));
+  }
+  mg_gpart[i] = part;
+  mg_bad[i] = (uint8_t)bad;
+}
+
+// ---- level 2: lane = message -----------------------------------------------
+// kSmall: one block of 1024 lanes, M < 1024; the 64-bit scan runs in the block.
+template <bool kSmall>
+__global__ __launch_bounds__(kSmall ? 1024 : 256) void k_enc_msg(mochi_write2_source s,
+                                                                 const uint32_t* __restrict__ id_off, uint32_t n_ids,
+                                                                 const uint64_t* __restrict__ mg_gpart,
+                                                                 const uint8_t* __restrict__ mg_bad,
+                                                                 uint32_t* __restrict__ mg_msg,
+                                                                 uint32_t* __restrict__ mg_rel,
+                                                                 uint32_t* __restrict__ msg_wc,
+                                                                 uint32_t* __restrict__ msg_tx,
+                                                                 uint32_t* __restrict__ msg_len,
+                                                                 uint8_t* __restrict__ status,
+                                                                 uint64_t* __restrict__ len64,
+                                                                 uint64_t* __restrict__ off64,
+                                                                 uint64_t* __restrict__ msg_off) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t M = s.n_msgs;
+  uint64_t mine = 0;
+  if (m < M) {
+    const uint32_t cl = s.client_off ? s.client_len[m] : 0;
+    bool bad_grant = false, bad_signer = false;
+    uint64_t wc = 0, tx = 0;
+    const uint32_t i1 = s.cert_mg_off[m + 1];
+#pragma unroll 1
+    for (uint32_t i = s.cert_mg_off[m]; i < i1; i++) {
+      mg_msg[i] = m;
+      mg_rel[i] = (uint32_t)wc;
+      bad_grant |= mg_bad[i] != 0;
+      const uint32_t sg = s.mg_signer[i];
+      if (sg >= n_ids) {
+        bad_signer = true;
+        continue;
+      }
+      const uint32_t sl = id_off[sg + 1] - id_off[sg];
+      const uint64_t mg = mg_gpart[i] + enc_ld_opt_size(cl) + enc_ld_opt_size(sl);
+      wc += enc_ld_size(enc_ld_size(sl) + enc_ld_size(mg));
+    }
+    const uint32_t o1 = s.cert_op_off[m + 1];
+#pragma unroll 1
+    for (uint32_t o = s.cert_op_off[m]; o < o1; o++)
+      tx += enc_ld_size(enc_op_body(s.op_action[o], s.op1_len[o], s.op2_off ? s.op2_len[o] : 0));
+    const uint64_t len = enc_ld_opt_size(wc) + enc_ld_opt_size(tx);
+    const uint8_t st = bad_grant ? MOCHI_ENC_BAD_GRANT : bad_signer ? MOCHI_ENC_BAD_SIGNER
+                       : len > kEncMaxMsg ? MOCHI_ENC_TOO_LONG : MOCHI_ENC_OK;
+    mine = st == MOCHI_ENC_OK ? len : 0;
+    status[m] = st;
+    msg_len[m] = (uint32_t)mine;
+    msg_wc[m] = (uint32_t)wc;
+    msg_tx[m] = (uint32_t)tx;
+  }
+  if constexpr (kSmall) {
+    using Scan = hipcub::BlockScan<uint64_t, 1024>;
+    __shared__ typename Scan::TempStorage tmp;
+    uint64_t off;
+    Scan(tmp).ExclusiveSum(mine, off);
+    if (m < M) msg_off[m] = off;
+    if (m == M) off64[M] = off;
+  } else {
+    if (m <= M) len64[m] = mine;
+  }
+}
+
+// ---- short byte runs --------------------------------------------------------
+// A lane's header bytes lie in runs of ~30 between the payloads it skips.  The
+// bytes are gathered into the aligned dword they fall in and go out as one
+// dword store once the lane has written all four; the partial dword at either
+// end of a run (its other bytes are payload or another lane's header) is
+// written with byte stores.  ~3x fewer scattered stores than byte by byte.
+struct Put {
+  uint8_t* p;      // address of the next byte
+  uint32_t w = 0;  // bytes gathered for the dword that holds p - 1
+  uint32_t n = 0;  // how many (they end at p)
+  __device__ __forceinline__ explicit Put(uint8_t* at) : p(at) {}
+  __device__ __forceinline__ void flush() {
+    if (n == 4) {
+      *(uint32_t*)(p - 4) = w;  // n == 4 only when p is dword-aligned (byte())
+    } else {
+      const uint32_t sh = 8 * (uint32_t)((uintptr_t)(p - n) & 3);
+#pragma unroll 1
+      for (uint32_t k = 0; k < n; k++) (p - n)[k] = (uint8_t)(w >> (sh + 8 * k));
+    }
+    w = 0;
+    n = 0;
+  }
+  __device__ __forceinline__ void byte(uint32_t b) {
+    w |= (b & 0xFFu) << (8 * (uint32_t)((uintptr_t)p & 3));
+    p++;
+    n++;
+    if (((uintptr_t)p & 3) == 0) flush();  // the dword is complete (n == 4) or its head was not ours (n < 4)
+  }
+  // leave a payload of `len` bytes to k_enc_copy
+  __device__ __forceinline__ void skip(uint32_t len) {
+    flush();
+    p += len;
+  }
+  __device__ __forceinline__ void varint(uint64_t v) {
+#pragma unroll 1
+    while (v >= 0x80) {
+      byte((uint32_t)v | 0x80);
+      v >>= 7;
+    }
+    byte((uint32_t)v);
+  }
+  // The source is read as the aligned words that hold it, four independent
+  // loads at a time (a word is loaded only if it holds a byte of the run, as
+  // ByteReader's): a quarter of the load instructions of a byte-wise copy and
+  // one load latency per 16 bytes (ids and keys are 10-30 bytes).
+  __device__ __forceinline__ void bytes(const uint8_t* __restrict__ q, uint32_t len) {
+    if (!len) return;
+    const uintptr_t a = (uintptr_t)q;
+    const uint32_t* wp = (const uint32_t*)(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3), nw = (sh + len + 3) >> 2;
+#pragma unroll 1
+    for (uint32_t w0 = 0; w0 < nw; w0 += 4) {
+      uint32_t t[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) t[j] = w0 + j < nw ? wp[w0 + j] : 0u;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          const uint32_t idx = 4 * (w0 + j) + b;  // byte index counted from wp
+          if (idx >= sh && idx < sh + len) byte(t[j] >> (8 * b));
+        }
+    }
+  }
+  __device__ __forceinline__ void ld(uint32_t tag, const uint8_t* __restrict__ q, uint32_t len) {
+    byte(tag);
+    varint(len);
+    bytes(q, len);
+  }
+};
+
+// ---- headers: lane = MultiGrant --------------------------------------------
+__global__ __launch_bounds__(256) void k_enc_hdr_mg(mochi_write2_source s, const uint8_t* __restrict__ ids,
+                                                    const uint32_t* __restrict__ id_off,
+                                                    const uint32_t* __restrict__ g_oid,
+                                                    const uint64_t* __restrict__ mg_gpart,
+                                                    const uint32_t* __restrict__ mg_msg,
+                                                    const uint32_t* __restrict__ mg_rel,
+                                                    const uint32_t* __restrict__ msg_wc,
+                                                    const uint64_t* __restrict__ msg_off,
+                                                    const uint8_t* __restrict__ status, uint8_t* __restrict__ wire,
+                                                    uint64_t* __restrict__ g_dst) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s.n_mgs) return;
+  const uint32_t m = mg_msg[i];
+  if (m == 0xFFFFFFFFu || status[m] != MOCHI_ENC_OK) return;  // g_dst stays kNone: nothing to copy
+  const uint32_t cl = s.client_off ? s.client_len[m] : 0;
+  const uint32_t sg = s.mg_signer[i];
+  const uint8_t* sid = ids + id_off[sg];
+  const uint32_t sl = id_off[sg + 1] - id_off[sg];
+  const uint64_t mg = mg_gpart[i] + enc_ld_opt_size(cl) + enc_ld_opt_size(sl);
+  uint8_t* const base = wire + msg_off[m];
+  Put o(base + 1 + enc_varint_size(msg_wc[m]) + mg_rel[i]);
+  o.byte(0x0A);
+  o.varint(enc_ld_size(sl) + enc_ld_size(mg));
+  o.ld(0x0A, sid, sl);
+  o.byte(0x12);
+  o.varint(mg);
+  const uint32_t g0 = s.mg_grant_off[i], g1 = s.mg_grant_off[i + 1];
+#pragma unroll 1
+  for (uint32_t g = g0; g < g1; g++) {
+    const uint8_t* gb = s.grant_bytes + s.grant_off[g];
+    const uint32_t gl = s.grant_len[g], oo = g_oid[2 * (size_t)g], ol = g_oid[2 * (size_t)g + 1];
+    o.byte(0x0A);
+    o.varint(enc_e1_body(ol, gl));
+    o.ld(0x0A, gb + oo, ol);
+    o.byte(0x12);
+    o.varint(gl);
+    g_dst[2 * (size_t)g] = (uint64_t)(o.p - wire);
+    o.skip(gl);
+  }
+  if (cl) o.ld(0x12, s.strings + s.client_off[m], cl);
+  if (sl) o.ld(0x22, sid, sl);
+  if (s.sig) {
+#pragma unroll 1
+    for (uint32_t g = g0; g < g1; g++) {
+      const uint8_t* gb = s.grant_bytes + s.grant_off[g];
+      const uint32_t oo = g_oid[2 * (size_t)g], ol = g_oid[2 * (size_t)g + 1];
+      o.byte(0x2A);
+      o.varint(enc_e5_body(ol));
+      o.ld(0x0A, gb + oo, ol);
+      o.byte(0x12);
+      o.byte(0x80);
+      o.byte(0x02);
+      g_dst[2 * (size_t)g + 1] = (uint64_t)(o.p - wire);
+      o.skip(MOCHI_RSA_BYTES);
+    }
+  }
+  o.flush();
+}
+
+// ---- headers: lane = message (top level + the operations) -------------------
+__global__ __launch_bounds__(256) void k_enc_hdr_msg(mochi_write2_source s, const uint32_t* __restrict__ msg_wc,
+                                                     const uint32_t* __restrict__ msg_tx,
+                                                     const uint64_t* __restrict__ msg_off,
+                                                     const uint8_t* __restrict__ status, uint8_t* __restrict__ wire) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= s.n_msgs || status[m] != MOCHI_ENC_OK) return;
+  Put o(wire + msg_off[m]);
+  const uint32_t wc = msg_wc[m], tx = msg_tx[m];
+  if (wc) {
+    o.byte(0x0A);
+    o.varint(wc);
+    o.skip(wc);
+  }
+  if (!tx) return;
+  o.byte(0x12);
+  o.varint(tx);
+  const uint32_t q1 = s.cert_op_off[m + 1];
+#pragma unroll 1
+  for (uint32_t q = s.cert_op_off[m]; q < q1; q++) {
+    const uint32_t act = s.op_action[q], l1 = s.op1_len[q], l2 = s.op2_off ? s.op2_len[q] : 0;
+    o.byte(0x0A);
+    o.varint(enc_op_body(act, l1, l2));
+    if (act) {
+      o.byte(0x08);
+      o.varint(act);
+    }
+    if (l1) o.ld(0x12, s.strings + s.op1_off[q], l1);
+    if (l2) o.ld(0x1A, s.strings + s.op2_off[q], l2);
+  }
+  o.flush();
+}
+
+// ---- payload copy -------------------------------------------------------------
+// 16-byte-aligned destination chunks holding a byte of the run [d0, d0 + len)
+__device__ __forceinline__ uint32_t run_chunks(uintptr_t d0, uint32_t len) {
+  return len ? (uint32_t)(((d0 + len - 1) >> 4) - (d0 >> 4)) + 1 : 0;
+}
+
+// Destination chunk c of the run src[0, len) -> [d0, d0 + len).  The lane owns
+// the aligned chunk and assembles its 16 bytes from the one or two aligned
+// SOURCE chunks that hold them: a dword rotation (mask selects) plus a funnel
+// shift, k_w2_sig's read-side trick.  A source chunk is loaded only when it
+// holds a payload byte (in bounds, as ByteReader's words).  A chunk that is all
+// payload goes out as one dwordx4; the first / last partial chunk of a run is
+// written with byte and short stores only, because its other bytes belong to
+// headers written by another lane or kernel (a read-modify-write would race).
+__device__ __forceinline__ void copy_chunk(uintptr_t d0, const uint8_t* __restrict__ src, uint32_t len, uint32_t c) {
+  const uintptr_t A = (d0 & ~(uintptr_t)15) + 16 * (uintptr_t)c, dend = d0 + len;
+  const uint32_t lo = A < d0 ? (uint32_t)(d0 - A) : 0;
+  const uint32_t hi = dend - A < 16 ? (uint32_t)(dend - A) : 16;
+  const uintptr_t S = (uintptr_t)src + (A - d0);  // source address of the chunk's byte 0 (modular when A < d0)
+  const uint4* cp = (const uint4*)(S & ~(uintptr_t)15);
+  const uint32_t sh = (uint32_t)(S & 15);
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  const uint4 c0 = lo < 16 - sh ? cp[0] : z;  // holds source bytes [lo, 16 - sh) of the chunk
+  const uint4 c1 = sh + hi > 16 ? cp[1] : z;  // holds [16 - sh, hi)
+  const uint32_t d[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const uint32_t m4 = 0u - ((sh >> 2) & 1u), m8 = 0u - ((sh >> 3) & 1u);
+  uint32_t e1[7], e[5];
+#pragma unroll
+  for (int j = 0; j < 7; j++) e1[j] = (d[j + 1] & m4) | (d[j] & ~m4);
+#pragma unroll
+  for (int j = 0; j < 5; j++) e[j] = (e1[j + 2] & m8) | (e1[j] & ~m8);
+  const uint32_t r = 8 * (sh & 3);
+  const uint4 v = make_uint4(__builtin_amdgcn_alignbit(e[1], e[0], r), __builtin_amdgcn_alignbit(e[2], e[1], r),
+                             __builtin_amdgcn_alignbit(e[3], e[2], r), __builtin_amdgcn_alignbit(e[4], e[3], r));
+  if (lo == 0 && hi == 16) {
+    *(uint4*)A = v;
+    return;
+  }
+#pragma unroll 1
+  for (uint32_t i = lo; i < hi;) {
+    const uint32_t w = (i < 4 ? v.x : i < 8 ? v.y : i < 12 ? v.z : v.w) >> (8 * (i & 3));
+    if (!(i & 1) && i + 2 <= hi) {
+      *(uint16_t*)(A + i) = (uint16_t)w;
+      i += 2;
+    } else {
+      *(uint8_t*)(A + i) = (uint8_t)w;
+      i++;
+    }
+  }
+}
+
+// 16 lanes per grant: its bytes, then its signature, as one list of chunks
+__global__ __launch_bounds__(256) void k_enc_copy(mochi_write2_source s, const uint64_t* __restrict__ g_dst,
+                                                  uint8_t* __restrict__ wire) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t g = t >> 4;
+  const uint32_t q = (uint32_t)(t & 15);
+  if (g >= s.n_grants) return;
+  const uint64_t dg = g_dst[2 * g], ds = g_dst[2 * g + 1];
+  if (dg == kNone) return;  // a grant of no emitted message
+  const uint32_t gl = s.grant_len[g];
+  const uintptr_t d0 = (uintptr_t)(wire + dg);
+  const uint8_t* src = s.grant_bytes + s.grant_off[g];
+  const uint32_t n1 = run_chunks(d0, gl);
+  uint32_t c = q;
+#pragma unroll 1
+  for (; c < n1; c += 16) copy_chunk(d0, src, gl, c);
+  if (ds == kNone) return;
+  const uintptr_t d1 = (uintptr_t)(wire + ds);
+  const uint32_t n2 = run_chunks(d1, MOCHI_RSA_BYTES);
+  const uint8_t* sg = s.sig + (size_t)MOCHI_RSA_BYTES * g;
+#pragma unroll 1
+  for (c -= n1; c < n2; c += 16) copy_chunk(d1, sg, MOCHI_RSA_BYTES, c);
+}
+
+inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+}  // namespace
+
+size_t w2_enc_scratch_bytes(uint32_t M, uint32_t n_mgs, uint32_t N) {
+  const size_t m1 = (size_t)M + 1, nm = n_mgs, n = N;
+  return up16(16 * n) + up16(4 * nm) + up16(8 * n) + up16(8 * nm) + up16(4 * nm) + up16(nm) + 2 * up16(4 * m1) +
+         2 * up16(8 * m1) + 16;
+}
+
+void w2_enc_carve(W2EncArgs& a, void* base) {
+  const size_t m1 = (size_t)a.src.n_msgs + 1, nm = a.src.n_mgs, n = a.src.n_grants;
+  uint8_t* p = (uint8_t*)(((uintptr_t)base + 15) & ~(uintptr_t)15);
+  auto take = [&](size_t bytes) {
+    uint8_t* q = p;
+    p += up16(bytes);
+    return q;
+  };
+  a.g_dst = (uint64_t*)take(16 * n);  // g_dst and mg_msg adjacent: one fill (launch_w2_enc_size)
+  a.mg_msg = (uint32_t*)take(4 * nm);
+  a.g_oid = (uint32_t*)take(8 * n);
+  a.mg_gpart = (uint64_t*)take(8 * nm);
+  a.mg_rel = (uint32_t*)take(4 * nm);
+  a.mg_bad = (uint8_t*)take(nm);
+  a.msg_wc = (uint32_t*)take(4 * m1);
+  a.msg_tx = (uint32_t*)take(4 * m1);
+  a.len64 = (uint64_t*)take(8 * m1);
+  a.off64 = (uint64_t*)take(8 * m1);
+}
+
+hipError_t w2_enc_scan_temp_bytes(uint32_t n, size_t* bytes) {
+  return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n);
+}
+
+hipError_t launch_w2_enc_size(const W2EncArgs& a, hipStream_t st) {
+  const mochi_write2_source& s = a.src;
+  const uint32_t M = s.n_msgs;
+  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  hipError_t e = stamp(0);
+  if (e != hipSuccess) return e;
+  // "no destination" / "no message" until the header kernels say otherwise
+  const size_t fill = (size_t)((uint8_t*)(a.mg_msg + s.n_mgs) - (uint8_t*)a.g_dst);
+  if (fill && (e = hipMemsetAsync(a.g_dst, 0xFF, fill, st)) != hipSuccess) return e;
+  if (s.n_mgs) hipLaunchKernelGGL(k_enc_mg, dim3(cdiv(s.n_mgs, 256)), dim3(256), 0, st, s, a.g_oid, a.mg_gpart, a.mg_bad);
+  if ((e = stamp(1)) != hipSuccess) return e;
+  if (w2_small(M)) {
+    hipLaunchKernelGGL(k_enc_msg<true>, dim3(1), dim3(1024), 0, st, s, a.id_off, a.n_ids, a.mg_gpart, a.mg_bad, a.mg_msg,
+                       a.mg_rel, a.msg_wc, a.msg_tx, a.msg_len, a.status, a.len64, a.off64, a.msg_off);
+    if ((e = stamp(2)) != hipSuccess || (e = stamp(3)) != hipSuccess) return e;
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_enc_msg<false>, dim3(cdiv((uint64_t)M + 1, 256)), dim3(256), 0, st, s, a.id_off, a.n_ids,
+                     a.mg_gpart, a.mg_bad, a.mg_msg, a.mg_rel, a.msg_wc, a.msg_tx, a.msg_len, a.status, a.len64,
+                     a.off64, a.msg_off);
+  e = hipGetLastError();
+  if (e != hipSuccess || (e = stamp(2)) != hipSuccess) return e;
+  size_t tb = a.scan_temp_bytes;
+  e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.len64, a.off64, (int)(M + 1), st);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(a.msg_off, a.off64, 8 * (size_t)M, hipMemcpyDeviceToDevice, st);
+  return e != hipSuccess ? e : stamp(3);
+}
+
+hipError_t launch_w2_enc_emit(const W2EncArgs& a, hipStream_t st) {
+  const mochi_write2_source& s = a.src;
+  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  hipError_t e = stamp(4);
+  if (e != hipSuccess) return e;
+  if (s.n_mgs)
+    hipLaunchKernelGGL(k_enc_hdr_mg, dim3(cdiv(s.n_mgs, 256)), dim3(256), 0, st, s, a.ids, a.id_off, a.g_oid, a.mg_gpart,
+                       a.mg_msg, a.mg_rel, a.msg_wc, a.msg_off, a.status, a.wire, a.g_dst);
+  if ((e = stamp(5)) != hipSuccess) return e;
+  if (s.n_msgs)
+    hipLaunchKernelGGL(k_enc_hdr_msg, dim3(cdiv(s.n_msgs, 256)), dim3(256), 0, st, s, a.msg_wc, a.msg_tx, a.msg_off,
+                       a.status, a.wire);
+  if ((e = stamp(6)) != hipSuccess) return e;
+  if (s.n_grants)
+    hipLaunchKernelGGL(k_enc_copy, dim3(cdiv((uint64_t)s.n_grants * 16, 256)), dim3(256), 0, st, s, a.g_dst, a.wire);
+  e = hipGetLastError();
+  return e != hipSuccess ? e : stamp(7);
+}
+
+}  // namespace mochi

@@ -181,6 +181,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_verify_write2_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mochi_write2_decode.argtypes = [vp, vp, vp]
     lib.mochi_write2_decoded_free.argtypes = [vp]
+    lib.mochi_write2_encode_bound.restype = ctypes.c_uint64
+    lib.mochi_write2_encode_bound.argtypes = [vp, u32]
+    lib.mochi_write2_encode.argtypes = [vp, vp, vp, u32, vp, ctypes.c_uint64, vp, vp, vp, vp]
+    lib.mochi_write2_encode_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp]
+    lib.mochi_ctx_read_encode_profile.argtypes = [vp, vp, u32]
     lib.mochi_signer_create.restype = vp
     lib.mochi_signer_create.argtypes = [ctypes.c_int, ctypes.c_char_p]
     lib.mochi_signer_destroy.argtypes = [vp]
@@ -511,6 +516,33 @@ class Verifier:
         if rc != OK:
             raise MochiError(f"mochi_verify_write2_device rc={rc}: {_err(self.lib)}")
 
+    def encode_write2_device(self, dsrc: "DeviceWrite2Source", wire, msg_off, msg_len, status, stream: int = 0,
+                             check: bool = True):
+        """Device-resident certificate source -> Write2ToServer bodies in `wire` (torch
+        uint8) with msg_off (int64) / msg_len (int32) / status (uint8) [M], all on the
+        device (mochi_write2_encode_device).  Waits for the total size, then returns
+        (rc, wire_len) with the emit kernels enqueued on `stream`.  rc is EINVAL with
+        wire_len = the size needed when `wire` is too small (nothing written);
+        check=True raises on any rc but OK."""
+        sc = dsrc.to_c()
+        n = ctypes.c_uint64(0)
+        cap = int(wire.numel()) if wire is not None else 0
+        rc = self.lib.mochi_write2_encode_device(self.ctx, ctypes.addressof(sc), wire.data_ptr() if cap else None, cap,
+                                                 msg_off.data_ptr(), msg_len.data_ptr(), status.data_ptr(),
+                                                 ctypes.addressof(n), stream or None)
+        if check and rc != OK:
+            raise MochiError(f"mochi_write2_encode_device rc={rc}: {_err(self.lib)}")
+        return rc, int(n.value)
+
+    ENCODE_KERNELS = ("k_enc_mg", "k_enc_msg", "scan", "k_enc_hdr_mg", "k_enc_hdr_msg", "k_enc_copy")
+
+    def read_encode_profile(self) -> dict:
+        """Per-kernel ms of the last encode_write2_device call made with set_profiling(True)."""
+        ms = np.zeros(len(self.ENCODE_KERNELS), np.float32)
+        if self.lib.mochi_ctx_read_encode_profile(self.ctx, _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_encode_profile: {_err(self.lib)}")
+        return dict(zip(self.ENCODE_KERNELS, (float(x) for x in ms)))
+
     def decode_write2(self, wb) -> dict:
         """The device decoder's SoA view of the messages (inspection / tests)."""
         wc, keep = write2_batch_c(wb)
@@ -689,6 +721,29 @@ class DeviceWireBatch:
         ots = getattr(wb, "op_object_ts", None)
         self.op_object_ts = None if ots is None or wb.op_flags_off is None else t(np.ascontiguousarray(ots, np.int64))
         self.status = torch.zeros(max(self.n_msgs, 1), dtype=torch.uint8, device=dev)
+
+    @classmethod
+    def from_encoded(cls, wire, msg_off, msg_len, n_msgs: int, expected_hash, op_flags_off=None, op_flags=None,
+                     op_object_ts=None) -> "DeviceWireBatch":
+        """The device outputs of Verifier.encode_write2_device (wire / msg_off /
+        msg_len tensors, used as they are: no copy, no host round trip) as the input
+        of verify_write2_device.  expected_hash [M, 128] and the optional per-op
+        arrays may be numpy arrays or tensors on the same device."""
+        import torch
+
+        dev = wire.device
+        t = lambda a, dt: a.to(dev) if isinstance(a, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(a).view(dt)).to(dev)
+        self = cls.__new__(cls)
+        self.n_msgs = int(n_msgs)
+        self.wire, self.msg_off, self.msg_len = wire, msg_off, msg_len
+        self.op_flags_off = None if op_flags_off is None else t(op_flags_off, np.int32)
+        self.op_flags = (torch.zeros(1, dtype=torch.uint8, device=dev) if op_flags is None or len(op_flags) == 0
+                         else t(op_flags, np.uint8))
+        self.expected_hash = t(expected_hash, np.uint8).reshape(-1)
+        self.op_object_ts = None if op_object_ts is None or op_flags_off is None else t(op_object_ts, np.int64)
+        self.status = torch.zeros(max(self.n_msgs, 1), dtype=torch.uint8, device=dev)
+        return self
 
     def to_c(self) -> "Write2Batch_C":
         c = Write2Batch_C()
@@ -944,6 +999,161 @@ def write2_batch_c(wb):
     c.op_flags_off, c.op_flags, c.expected_hash = _ptr(arrs[3]), _ptr(arrs[4]), _ptr(arrs[5])
     c.op_object_ts = _ptr(arrs[6])
     return c, arrs
+
+
+
+# ---------------------------------------------------------------------------
+# Write2ToServer encode (client certificate assembly, MochiDBClient.java:333-338)
+# ---------------------------------------------------------------------------
+ENC_OK, ENC_BAD_GRANT, ENC_BAD_SIGNER, ENC_TOO_LONG = 0, 1, 2, 3
+
+
+class Write2Source_C(ctypes.Structure):
+    _fields_ = [("n_msgs", ctypes.c_uint32), ("n_mgs", ctypes.c_uint32), ("n_grants", ctypes.c_uint32),
+                ("n_ops", ctypes.c_uint32),
+                ("grant_bytes", ctypes.c_void_p), ("grant_bytes_len", ctypes.c_uint64),
+                ("grant_off", ctypes.c_void_p), ("grant_len", ctypes.c_void_p), ("sig", ctypes.c_void_p),
+                ("cert_mg_off", ctypes.c_void_p), ("mg_grant_off", ctypes.c_void_p), ("mg_signer", ctypes.c_void_p),
+                ("strings", ctypes.c_void_p), ("strings_len", ctypes.c_uint64),
+                ("cert_op_off", ctypes.c_void_p), ("op_action", ctypes.c_void_p),
+                ("op1_off", ctypes.c_void_p), ("op1_len", ctypes.c_void_p),
+                ("op2_off", ctypes.c_void_p), ("op2_len", ctypes.c_void_p),
+                ("client_off", ctypes.c_void_p), ("client_len", ctypes.c_void_p)]
+
+
+@dataclass
+class Write2Source:
+    """SoA source of M Write2ToServer messages (mochi_write2_source, host arrays)."""
+
+    grant_bytes: np.ndarray  # uint8
+    grant_off: np.ndarray  # uint64 [N]
+    grant_len: np.ndarray  # uint32 [N]
+    sig: Optional[np.ndarray]  # uint8 [N, 256] or None = no grantSignatures entries
+    cert_mg_off: np.ndarray  # uint32 [M+1]
+    mg_grant_off: np.ndarray  # uint32 [n_mgs+1]
+    mg_signer: np.ndarray  # uint16 [n_mgs]
+    strings: np.ndarray  # uint8: operands and client ids
+    cert_op_off: np.ndarray  # uint32 [M+1]
+    op_action: np.ndarray  # uint8 [O]
+    op1_off: np.ndarray  # uint64 [O]
+    op1_len: np.ndarray  # uint32 [O]
+    op2_off: Optional[np.ndarray] = None
+    op2_len: Optional[np.ndarray] = None
+    client_off: Optional[np.ndarray] = None  # uint64 [M]
+    client_len: Optional[np.ndarray] = None  # uint32 [M]
+
+    DTYPES = dict(grant_bytes=np.uint8, grant_off=np.uint64, grant_len=np.uint32, sig=np.uint8, cert_mg_off=np.uint32,
+                  mg_grant_off=np.uint32, mg_signer=np.uint16, strings=np.uint8, cert_op_off=np.uint32,
+                  op_action=np.uint8, op1_off=np.uint64, op1_len=np.uint32, op2_off=np.uint64, op2_len=np.uint32,
+                  client_off=np.uint64, client_len=np.uint32)
+
+    @property
+    def n_msgs(self) -> int:
+        return int(self.cert_mg_off.shape[0]) - 1
+
+    @property
+    def n_mgs(self) -> int:
+        return int(self.mg_signer.shape[0])
+
+    @property
+    def n_grants(self) -> int:
+        return int(self.grant_off.shape[0])
+
+    @property
+    def n_ops(self) -> int:
+        return int(self.op_action.shape[0])
+
+    def arrays(self) -> dict:
+        """Every array C-contiguous in its ABI dtype (None stays None)."""
+        out = {}
+        for k, dt in self.DTYPES.items():
+            a = getattr(self, k)
+            out[k] = None if a is None else np.ascontiguousarray(a, dt).reshape(-1)
+        return out
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write2Source_C()
+        c.n_msgs, c.n_mgs, c.n_grants, c.n_ops = self.n_msgs, self.n_mgs, self.n_grants, self.n_ops
+        c.grant_bytes_len = int(arrs["grant_bytes"].nbytes)
+        c.strings_len = int(arrs["strings"].nbytes)
+        for k, a in arrs.items():
+            # an empty array still gets a valid address (the library reads none of it)
+            setattr(c, k, None if a is None else _ptr(a if a.size else np.zeros(1, a.dtype)))
+        return c, arrs
+
+
+def _id_table(server_ids):
+    enc = [x.encode() if isinstance(x, str) else bytes(x) for x in server_ids]
+    blob = np.frombuffer(b"".join(enc) or b"\x00", np.uint8).copy()
+    off = np.zeros(len(enc) + 1, np.uint32)
+    np.cumsum([len(x) for x in enc], out=off[1:])
+    return blob, off, len(enc)
+
+
+def write2_encode_bound(src: "Write2Source", max_id_len: int) -> int:
+    """mochi_write2_encode_bound: a safe (not tight) upper bound on the wire size."""
+    c, keep = src.to_c()
+    return int(load_library().mochi_write2_encode_bound(ctypes.addressof(c), int(max_id_len)))
+
+
+def encode_write2_into(src: "Write2Source", server_ids, wire: Optional[np.ndarray]):
+    """mochi_write2_encode into the caller's buffer (uint8; None = capacity 0).
+    Returns (rc, wire_len, msg_off, msg_len, status); rc is EINVAL with wire_len =
+    the size needed when the buffer is too small (no byte of it written)."""
+    lib = load_library()
+    c, keep = src.to_c()
+    ids, id_off, n_ids = _id_table(server_ids)
+    M = src.n_msgs
+    msg_off = np.zeros(max(M, 1), np.uint64)
+    msg_len = np.zeros(max(M, 1), np.uint32)
+    status = np.zeros(max(M, 1), np.uint8)
+    n = ctypes.c_uint64(0)
+    cap = 0 if wire is None else int(wire.nbytes)
+    rc = lib.mochi_write2_encode(ctypes.addressof(c), _ptr(ids), _ptr(id_off), n_ids, _ptr(wire) if cap else None, cap,
+                                 _ptr(msg_off), _ptr(msg_len), _ptr(status), ctypes.addressof(n))
+    return rc, int(n.value), msg_off[:M], msg_len[:M], status[:M]
+
+
+def encode_write2(src: "Write2Source", server_ids):
+    """Host form of the Write2ToServer encoder: (wire uint8 [wire_len], msg_off
+    uint64 [M], msg_len uint32 [M], status uint8 [M]) for the source's messages,
+    laid out as mochi_write2_batch takes them.  server_ids[i] = the id of key i."""
+    lib = load_library()
+    rc, need, msg_off, msg_len, status = encode_write2_into(src, server_ids, None)  # sizes only
+    if rc != OK and need == 0:
+        raise MochiError(f"mochi_write2_encode rc={rc}: {_err(lib)}")
+    wire = np.zeros(max(need, 1), np.uint8)
+    rc, n, msg_off, msg_len, status = encode_write2_into(src, server_ids, wire)
+    if rc != OK:
+        raise MochiError(f"mochi_write2_encode rc={rc}: {_err(lib)}")
+    return wire[:n], msg_off, msg_len, status
+
+
+class DeviceWrite2Source:
+    """A Write2Source copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, src: "Write2Source", device: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: np.uint8, np.uint16: np.int16, np.uint32: np.int32, np.uint64: np.int64}
+        self.n_msgs, self.n_mgs, self.n_grants, self.n_ops = src.n_msgs, src.n_mgs, src.n_grants, src.n_ops
+        for k, a in src.arrays().items():
+            if a is not None and a.size == 0:
+                a = np.zeros(1, a.dtype)
+            setattr(self, k, None if a is None else torch.from_numpy(a.view(sv[Write2Source.DTYPES[k]])).to(dev))
+        self.grant_bytes_len = int(np.asarray(src.grant_bytes).size)
+        self.strings_len = int(np.asarray(src.strings).size)
+
+    def to_c(self) -> Write2Source_C:
+        c = Write2Source_C()
+        c.n_msgs, c.n_mgs, c.n_grants, c.n_ops = self.n_msgs, self.n_mgs, self.n_grants, self.n_ops
+        c.grant_bytes_len, c.strings_len = self.grant_bytes_len, self.strings_len
+        for k in Write2Source.DTYPES:
+            t = getattr(self, k)
+            setattr(c, k, None if t is None else t.data_ptr())
+        return c
 
 
 class Write2Decoded_C(ctypes.Structure):

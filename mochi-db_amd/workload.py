@@ -402,6 +402,98 @@ def encode_wire_batch(s: Synth, server_ids=None, client_id: str = "", pad: int =
                      op_flags_off=ofo, op_flags=b.op_flags.copy(), expected_hash=b.expected_hash.copy())
 
 
+def _ragged_take(blob: np.ndarray, off: np.ndarray, ln: np.ndarray) -> np.ndarray:
+    """The slices blob[off[i] : off[i] + ln[i]] back to back (no Python loop)."""
+    ln = np.asarray(ln, np.int64)
+    start = np.zeros(ln.shape[0] + 1, np.int64)
+    np.cumsum(ln, out=start[1:])
+    idx = np.repeat(np.asarray(off, np.int64) - start[:-1], ln) + np.arange(int(start[-1]), dtype=np.int64)
+    return blob[idx]
+
+
+def _ascii_rows(strs: np.ndarray):
+    """A numpy string array as (uint8 [n, width] rows, lengths [n])."""
+    b = np.char.encode(strs, "ascii") if strs.size else np.zeros(0, "S1")
+    w = max(b.dtype.itemsize, 1)
+    rows = np.frombuffer(b.tobytes(), np.uint8).reshape(-1, w) if strs.size else np.zeros((0, 1), np.uint8)
+    return rows, np.char.str_len(b).astype(np.int64) if strs.size else np.zeros(0, np.int64)
+
+
+def write2_source(s: Synth, client_id: str = ""):
+    """The mochi_write2_source (mochi_hip.Write2Source) of exactly the messages
+    encode_wire_batch(s, client_id=client_id) builds: MultiGrants are the runs
+    of one signer inside a certificate, operand1 of an operation is the objectId
+    of the (last) grant with its key slot ("key-{slot}" when none has it),
+    operand2 is "value-{c}-{j}", the action is WRITE (2).  Grants must be
+    canonical with an objectId shorter than 128 bytes (as the synthetic ones
+    are).  Vectorised: no per-certificate Python loop."""
+    from mochi_hip import Write2Source
+
+    b = s.batch
+    C, N, O = b.n_certs, b.n_grants, b.n_ops
+    cgo = np.asarray(b.cert_grant_off, np.int64)
+    coo = np.asarray(b.cert_op_off, np.int64)
+    goff = np.asarray(b.grant_off[:N], np.int64)
+    glen = np.asarray(b.grant_len[:N], np.int64)
+    signer = np.asarray(b.signer[:N], np.int64)
+    cert_of_g = np.repeat(np.arange(C, dtype=np.int64), np.diff(cgo))
+    # MultiGrants: a new one where the signer or the certificate changes
+    first = np.ones(N, bool)
+    if N > 1:
+        first[1:] = (signer[1:] != signer[:-1]) | (cert_of_g[1:] != cert_of_g[:-1])
+    mg_start = np.nonzero(first)[0]
+    mg_grant_off = np.append(mg_start, N).astype(np.uint32)
+    cert_mg_off = np.zeros(C + 1, np.uint32)
+    np.cumsum(np.bincount(cert_of_g[mg_start], minlength=C), out=cert_mg_off[1:])
+    # objectId slice of each grant (canonical: field 1 first, one-byte length)
+    blob = np.asarray(b.grant_bytes, np.uint8)
+    has = glen >= 2
+    has[has] = blob[goff[has]] == 0x0A
+    ol = np.zeros(N, np.int64)
+    ol[has] = blob[goff[has] + 1]
+    assert (ol < 128).all(), "objectId of 128 bytes or more"
+    oo = goff + 2
+    if N == 0:  # operations without any grant: every operand1 is "key-{slot}"
+        ol, oo = np.zeros(1, np.int64), np.zeros(1, np.int64)
+    # operand1: the objectId of the last grant of the certificate with the op's key slot
+    cert_of_o = np.repeat(np.arange(C, dtype=np.int64), np.diff(coo))
+    j_of_o = np.arange(O, dtype=np.int64) - coo[cert_of_o]
+    okey = np.asarray(b.op_key[:O], np.int64)
+    gk = cert_of_g * 256 + np.asarray(b.grant_key[:N], np.int64)
+    uk, ridx = np.unique(gk[::-1], return_index=True)
+    last_g = N - 1 - ridx
+    want = cert_of_o * 256 + okey
+    pos = np.minimum(np.searchsorted(uk, want), max(uk.shape[0] - 1, 0))
+    found = (uk[pos] == want) if uk.size else np.zeros(O, bool)
+    og = np.where(found, last_g[pos] if uk.size else 0, 0)
+    miss_rows, miss_len = _ascii_rows(np.char.add("key-", okey[~found].astype(str)))
+    val_rows, val_len = _ascii_rows(np.char.add(np.char.add(np.char.add("value-", cert_of_o.astype(str)), "-"),
+                                                j_of_o.astype(str)))
+    l1 = np.where(found, ol[og], 0)
+    l1[~found] = miss_len
+    op1 = np.zeros(int(l1.sum()), np.uint8)
+    st1 = np.zeros(O + 1, np.int64)
+    np.cumsum(l1, out=st1[1:])
+    sel = np.repeat(found, l1)
+    op1[sel] = _ragged_take(blob, oo[og[found]], l1[found])
+    op1[~sel] = miss_rows[np.arange(miss_rows.shape[1])[None, :] < miss_len[:, None]]
+    op2 = val_rows[np.arange(val_rows.shape[1])[None, :] < val_len[:, None]]
+    st2 = np.zeros(O + 1, np.int64)
+    np.cumsum(val_len, out=st2[1:])
+    cid = np.frombuffer(client_id.encode(), np.uint8)
+    base2, basec = op1.shape[0], op1.shape[0] + op2.shape[0]
+    strings = np.concatenate([op1, op2, cid]) if basec + cid.size else np.zeros(1, np.uint8)
+    return Write2Source(
+        grant_bytes=blob, grant_off=goff.astype(np.uint64), grant_len=glen.astype(np.uint32),
+        sig=np.ascontiguousarray(b.sig[:N]), cert_mg_off=cert_mg_off, mg_grant_off=mg_grant_off,
+        mg_signer=signer[mg_start].astype(np.uint16), strings=strings,
+        cert_op_off=coo.astype(np.uint32), op_action=np.full(O, 2, np.uint8),
+        op1_off=st1[:-1].astype(np.uint64), op1_len=l1.astype(np.uint32),
+        op2_off=(base2 + st2[:-1]).astype(np.uint64), op2_len=val_len.astype(np.uint32),
+        client_off=np.full(C, basec, np.uint64) if cid.size else None,
+        client_len=np.full(C, cid.size, np.uint32) if cid.size else None)
+
+
 def server_id_table(n: int, server_ids=None):
     ids = (server_ids or SERVER_IDS)[:n]
     blob = "".join(ids).encode()
