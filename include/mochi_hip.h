@@ -593,6 +593,129 @@ int mochi_signer_rejected(mochi_signer* s, uint64_t* rejected);
 int mochi_signer_set_fault(mochi_signer* s, uint32_t grant_index);
 
 /* ------------------------------------------------------------------------
+ * Write1 grant issuance for a batch of Write1ToServer requests: which grants
+ * this server gives (InMemoryDataStore.java:105-155 processWrite, :233-310
+ * tryProcessWriteRegularly, StoreValueObjectContainer.java:100-133), their
+ * Grant bytes, and (device form) their signatures.
+ *
+ * The result equals processing the requests one after another in batch order,
+ * the ops of a request in transaction order, against the caller's state as of
+ * batch start (epochs do not move during Write1).  Per op:
+ *   action not WRITE / DELETE                          -> SKIP (no grant)
+ *   an earlier WRITE / DELETE op of the request had an
+ *   empty operand1 (the reference threw there)         -> SKIPPED (claims nothing)
+ *   the empty-key op itself                            -> FAILED
+ *   not LOCAL                                          -> WRONG_SHARD: a new Grant
+ *       {objectId, transactionHash, status = 1}, counted as granted; a later
+ *       non-local op of the same request on a byte-equal key refers to it
+ *   LOCAL without HAS_SVOC (DELETE of an absent key)   -> FAILED
+ *   LOCAL with HAS_SVOC: slot (object, ts), ts = op_epoch + req_seed (64-bit
+ *       wrapping, seed unsigned)
+ *     op_stored names a stored grant: RETRY (granted) when the request's
+ *       transactionHash byte-equals the stored one, else REFUSED; both refer
+ *       to the stored grant
+ *     slot free: the op with the smallest batch-wide op index among all ops
+ *       that reach the slot is NEW (Grant {objectId, timestamp = ts,
+ *       transactionHash}; a zero timestamp is omitted, proto3).  Every other
+ *       op on it is RETRY when its request's hash equals the winner's
+ *       request's, else REFUSED; both refer to the new grant.  A winner stays
+ *       the winner whatever becomes of its own request (the reference has
+ *       stored the grant by then, :139).
+ * Request kind: THROWS if any op FAILED, else REFUSED if any op REFUSED, else
+ * OK.  The reply's MultiGrant view lists each distinct grant once, at the first
+ * op that refers to it, in op order: the granted ops (NEW / RETRY /
+ * WRONG_SHARD) for OK, the REFUSED ops for REFUSED (:283-308), nothing for
+ * THROWS.  Java's HashMap iteration order is not reproduced: wire order is the
+ * caller's, as in mochi_write2_source.  New grants are numbered in the order of
+ * the ops that made them, so the host and device forms give identical arrays.
+ * Afterwards the host stores EVERY new grant, whatever its request's kind.
+ * ------------------------------------------------------------------------ */
+#define MOCHI_W1OP_LOCAL 0x01    /* objectBelongsToCurrentShardServer(operand1)            */
+#define MOCHI_W1OP_HAS_SVOC 0x02 /* the key has a container (a caller creates it for a
+                                    WRITE before the batch, as getOrCreateStoreValue does) */
+#define MOCHI_W1OP_WRITE 0x04    /* action == WRITE                                        */
+#define MOCHI_W1OP_DELETE 0x08   /* action == DELETE                                       */
+#define MOCHI_W1_NONE 0xFFFFFFFFu   /* op_stored: slot free; op_grant: no grant            */
+#define MOCHI_W1_STORED 0x80000000u /* op_grant / req_grant: MOCHI_W1_STORED | stored index */
+
+enum mochi_w1_op_decision {
+  MOCHI_W1D_SKIP = 0,
+  MOCHI_W1D_SKIPPED = 1,
+  MOCHI_W1D_FAILED = 2,
+  MOCHI_W1D_WRONG_SHARD = 3,
+  MOCHI_W1D_NEW = 4,
+  MOCHI_W1D_RETRY = 5,
+  MOCHI_W1D_REFUSED = 6,
+};
+enum mochi_w1_req_kind { MOCHI_W1K_OK = 0, MOCHI_W1K_REFUSED = 1, MOCHI_W1K_THROWS = 2 };
+
+typedef struct mochi_write1_batch {
+  uint32_t n_reqs, n_ops, n_stored;         /* n_ops below 2^30, n_stored below 2^31        */
+  const uint8_t*  strings; uint64_t strings_len; /* keys and hashes                         */
+  const uint32_t* req_op_off;    /* [Q+1] ops per request (at most MOCHI_MAX_OPS_PER_CERT)  */
+  const uint32_t* req_seed;      /* [Q]   Write1ToServer.seed                               */
+  const uint64_t* req_hash_off; const uint32_t* req_hash_len; /* [Q] transactionHash, any length */
+  const uint64_t* op_key_off;   const uint32_t* op_key_len;   /* [O] operand1                */
+  const uint8_t*  op_flags;      /* [O] MOCHI_W1OP_*                                        */
+  const uint32_t* op_obj;        /* [O] the caller's index of the key's container (LOCAL ops
+                                    only; equal keys <=> equal index; 0xFFFFFFFF reserved)  */
+  const int64_t*  op_epoch;      /* [O] the container's current epoch                       */
+  const uint32_t* op_stored;     /* [O] stored grant at (object, ts), or MOCHI_W1_NONE      */
+  const uint64_t* stored_hash_off; const uint32_t* stored_hash_len; /* [S] its transactionHash */
+} mochi_write1_batch;
+
+/* Every array is the caller's.  op_* and req_grant, grant_off / grant_len /
+ * grant_op / grant_ts (and sig, 256 bytes each) hold n_ops entries (n_new <=
+ * n_ops); n_new and grant_bytes_len are written by the call (host fields in
+ * both forms).  grant_bytes with grant_off / grant_len is the input layout of
+ * mochi_sign_batch_device, and with sig the grant part of mochi_write2_source. */
+typedef struct mochi_write1_issued {
+  uint8_t*  op_decision;   /* [O] mochi_w1_op_decision                                      */
+  uint32_t* op_grant;      /* [O] new-grant index, MOCHI_W1_STORED | stored index, or NONE  */
+  uint8_t*  req_kind;      /* [Q] mochi_w1_req_kind                                         */
+  uint32_t* req_grant_off; /* [Q+1] the reply's MultiGrant view                             */
+  uint32_t* req_grant;     /* [req_grant_off[Q]] grant references (as op_grant)             */
+  uint32_t  n_new;         /* out: new grants                                               */
+  uint64_t  grant_bytes_len; /* out: bytes of the new grants (the capacity needed)          */
+  uint8_t*  grant_bytes;  uint64_t grant_cap;  /* new grants back to back, in index order   */
+  uint64_t* grant_off;     /* [n_new]                                                       */
+  uint32_t* grant_len;     /* [n_new]                                                       */
+  uint32_t* grant_op;      /* [n_new] the op that made the grant                            */
+  int64_t*  grant_ts;      /* [n_new] its timestamp (0 for a WRONG_SHARD grant)             */
+  uint8_t*  sig;           /* [n_new][256] or NULL = do not sign (device form only)         */
+} mochi_write1_issued;
+
+/* A safe upper bound on grant_bytes_len from n_ops and strings_len of
+ * `counts_only` alone (no pointer is dereferenced): every op a new grant with a
+ * key and a hash of strings_len bytes each. */
+uint64_t mochi_write1_issue_bound(const mochi_write1_batch* counts_only);
+
+/* Host form: host arrays, no GPU, no key; `sig` is ignored.  MOCHI_EINVAL for a
+ * req_op_off that is not a CSR over n_ops, a slice outside `strings`, more than
+ * MOCHI_MAX_OPS_PER_CERT ops in a request, a stored index >= n_stored, or LOCAL
+ * ops with equal op_obj and different op_epoch.  When grant_cap is smaller than
+ * the size needed the call returns MOCHI_EINVAL with out->grant_bytes_len (and
+ * *bytes_needed, which may be NULL) = that size and out->n_new set, having
+ * written op_decision, req_kind and req_grant_off and nothing else. */
+int mochi_write1_issue(const mochi_write1_batch* batch, mochi_write1_issued* out, uint64_t* bytes_needed);
+
+/* Device form: every array of `batch` and `out` in DEVICE memory (the structs
+ * themselves on the host); scratch hangs off the signer.  The call waits once,
+ * for n_new and the byte total, then returns with the emit kernels and, when
+ * out->sig is not NULL, k_rsa_sign and the public-key check over the new grants
+ * enqueued on `stream`.  Same outputs and capacity rule as the host form; the
+ * inputs are trusted. */
+int mochi_write1_issue_device(mochi_signer* s, const mochi_write1_batch* batch, mochi_write1_issued* out,
+                              void* stream);
+/* Per-kernel device time (ms) of the last mochi_write1_issue_device call made
+ * while profiling was on: [0] table clear + k_w1_pre, [1] k_w1_claim,
+ * [2] k_w1_decide, [3] k_w1_reply (count), [4] the 64-bit scans, [5] k_w1_emit,
+ * [6] k_w1_reply (write), [7] k_rsa_sign + the public-key check (0 without
+ * sig).  Waits for that call.  n <= 8. */
+int mochi_signer_set_profiling(mochi_signer* s, int on);
+int mochi_signer_read_issue_profile(mochi_signer* s, float* kernel_ms, uint32_t n);
+
+/* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps
  * (Write2ToServerRequestHandler.handle -> processWrite2ToServer on a 2..20
  * thread pool, MochiServer.java:36-40), coalesced across threads into one

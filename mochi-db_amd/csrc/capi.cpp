@@ -22,6 +22,7 @@
 #include "../../include/mochi_hip.h"
 #include "kernels.h"
 #include "mont.h"
+#include "w1_issue.h"
 #include "w2.h"
 #include "w2_encode.h"
 #include "w2_host.h"
@@ -2061,6 +2062,14 @@ struct mochi_signer {
   mochi_ctx* check = nullptr;
   DevBuf zeros, flags, misc;  // signer index / key slot zeros, SIG_OK flags, [0] rejected [1..] CSR zeros
   uint32_t fault_idx = 0xFFFFFFFFu;
+  // Write1 issuance (w1_issue.hip): per-call scratch, scan temp, the two totals on the host
+  DevBuf w1_scratch, w1_scan;
+  PinnedBuf w1_tot;
+  hipEvent_t ev_tot = nullptr, ev_scratch = nullptr;  // totals landed; last user of the scratch done
+  bool scratch_used = false;
+  hipStream_t scratch_st = nullptr;
+  bool profiling = false, w1_ev_valid = false;
+  std::vector<hipEvent_t> w1_ev;  // kW1Events, created on first use
 };
 
 namespace {
@@ -2152,6 +2161,8 @@ mochi_signer* mochi_signer_create(int device, const char* pem) {
   int save = 0;
   (void)hipGetDevice(&save);
   ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
+       hipEventCreateWithFlags(&s->ev_tot, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&s->ev_scratch, hipEventDisableTiming) == hipSuccess &&
        hipMalloc(&s->d_key, host.size()) == hipSuccess &&
        hipMemcpy(s->d_key, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
   memset(host.data(), 0, host.size());
@@ -2187,6 +2198,9 @@ void mochi_signer_destroy(mochi_signer* s) {
     (void)hipFree(s->d_key);
   }
   if (s->stream) (void)hipStreamDestroy(s->stream);
+  if (s->ev_tot) (void)hipEventDestroy(s->ev_tot);
+  if (s->ev_scratch) (void)hipEventDestroy(s->ev_scratch);
+  for (auto e : s->w1_ev) (void)hipEventDestroy(e);
   if (s->check) mochi_ctx_destroy(s->check);
   delete s;
   (void)hipSetDevice(save);
@@ -2309,6 +2323,144 @@ int mochi_sign_batch(mochi_signer* s, const uint8_t* grant_bytes, uint64_t grant
   if (e == hipSuccess) memcpy(sig_out, s->pin_out.p, sig_bytes);
   (void)hipSetDevice(save);
   return e == hipSuccess ? MOCHI_OK : fail(MOCHI_EHIP, "sign batch: %s", hipGetErrorString(e));
+}
+
+}  // extern "C"
+
+// ---- Write1 grant issuance (w1_issue.hip / w1_issue_host.cpp) ------------------
+namespace {
+
+int check_write1(const mochi_write1_batch* b, const mochi_write1_issued* o) {
+  if (!b || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (b->n_ops >= (1u << 30) || b->n_stored >= MOCHI_W1_STORED || b->n_reqs == 0xFFFFFFFFu)
+    return fail(MOCHI_EINVAL, "batch too large");
+  if (!b->req_op_off || !o->req_grant_off) return fail(MOCHI_EINVAL, "req_op_off / req_grant_off required");
+  if (b->n_reqs && (!b->req_seed || !b->req_hash_off || !b->req_hash_len || !o->req_kind))
+    return fail(MOCHI_EINVAL, "req_seed / req_hash_off / req_hash_len / req_kind required");
+  if (b->n_ops && (!b->op_key_off || !b->op_key_len || !b->op_flags || !b->op_obj || !b->op_epoch || !b->op_stored ||
+                   !o->op_decision || !o->op_grant || !o->req_grant || !o->grant_off || !o->grant_len || !o->grant_op ||
+                   !o->grant_ts))
+    return fail(MOCHI_EINVAL, "an op or grant array is missing");
+  if (b->n_stored && (!b->stored_hash_off || !b->stored_hash_len))
+    return fail(MOCHI_EINVAL, "stored_hash_off / stored_hash_len required");
+  if (b->strings_len && !b->strings) return fail(MOCHI_EINVAL, "strings required");
+  if (o->grant_cap && !o->grant_bytes) return fail(MOCHI_EINVAL, "grant_bytes required");
+  return MOCHI_OK;
+}
+
+int run_write1_issue_device(mochi_signer* s, const mochi_write1_batch* b, mochi_write1_issued* o, hipStream_t st) {
+  const uint32_t Q = b->n_reqs, O = b->n_ops;
+  int rc;
+  size_t scan_bytes = 0;
+  if (!(mochi::w2_small(O) && mochi::w2_small(Q))) HIP_TRY(mochi::w1_scan_temp_bytes((O > Q ? O : Q) + 1, &scan_bytes));
+  if ((rc = s->w1_scratch.ensure(mochi::w1_scratch_bytes(Q, O))) || (rc = s->w1_scan.ensure(scan_bytes)) ||
+      (rc = s->w1_tot.ensure(16)))
+    return rc;
+  mochi::W1Args a;
+  memset(&a, 0, sizeof a);
+  a.b = *b;
+  a.o = *o;
+  a.slots = (uint32_t)mochi::w1_table_slots(O);
+  a.scan_temp = s->w1_scan.p;
+  a.scan_temp_bytes = s->w1_scan.cap;
+  mochi::w1_carve(a, s->w1_scratch.p);
+  s->w1_ev_valid = false;
+  if (s->profiling) {
+    while (s->w1_ev.size() < (size_t)mochi::kW1Events) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      s->w1_ev.push_back(e);
+    }
+    a.ev = s->w1_ev.data();
+  }
+  // one scratch per signer: a call on another stream waits for the last call's kernels
+  if (s->scratch_used && s->scratch_st != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_scratch, 0));
+  HIP_TRY(mochi::launch_w1_decide(a, st));
+  uint64_t* tot = (uint64_t*)s->w1_tot.p;
+  HIP_TRY(hipMemcpyAsync(tot, a.totals, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(s->ev_tot, st));
+  HIP_TRY(hipEventSynchronize(s->ev_tot));
+  o->n_new = (uint32_t)tot[0];
+  o->grant_bytes_len = tot[1];
+  const bool fits = tot[1] <= o->grant_cap;
+  if (fits) {
+    HIP_TRY(mochi::launch_w1_emit(a, st));
+    if (o->sig && o->n_new) {
+      HIP_TRY(mochi::launch_rsa_sign(o->grant_bytes, o->grant_off, o->grant_len, o->n_new, s->d_key, o->sig,
+                                     s->fault_idx, st));
+      std::lock_guard<std::mutex> ck(s->check->mu);
+      if ((rc = signer_check(s, o->grant_bytes, o->grant_off, o->grant_len, o->n_new, o->sig, st))) return rc;
+    }
+    if (a.ev) HIP_TRY(hipEventRecord(a.ev[mochi::kW1Events - 1], st));
+  }
+  s->w1_ev_valid = a.ev && fits;
+  s->scratch_used = true;
+  s->scratch_st = st;
+  HIP_TRY(hipEventRecord(s->ev_scratch, st));
+  if (!fits)
+    return fail(MOCHI_EINVAL, "grant_cap (%llu) is smaller than the size needed (%llu)", (unsigned long long)o->grant_cap,
+                (unsigned long long)tot[1]);
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mochi_write1_issue_bound(const mochi_write1_batch* b) {
+  if (!b) return 0;
+  // every op a new grant: key and hash at strings_len each, ten-byte varints throughout
+  const unsigned __int128 t = (unsigned __int128)b->n_ops * (2 * (unsigned __int128)b->strings_len + 40);
+  return t > ~0ull ? ~0ull : (uint64_t)t;
+}
+
+int mochi_write1_issue(const mochi_write1_batch* b, mochi_write1_issued* o, uint64_t* bytes_needed) {
+  if (bytes_needed) *bytes_needed = 0;
+  int rc = check_write1(b, o);
+  if (rc) return rc;
+  o->n_new = 0;
+  o->grant_bytes_len = 0;
+  const char* err = "";
+  rc = mochi_host::write1_issue(b, o, &err);
+  if (bytes_needed) *bytes_needed = o->grant_bytes_len;
+  return rc ? fail(rc, "mochi_write1_issue: %s", err) : MOCHI_OK;
+}
+
+int mochi_write1_issue_device(mochi_signer* s, const mochi_write1_batch* b, mochi_write1_issued* o, void* stream) {
+  if (!s) return fail(MOCHI_EINVAL, "null signer");
+  int rc = check_write1(b, o);
+  if (rc) return rc;
+  o->n_new = 0;
+  o->grant_bytes_len = 0;
+  std::lock_guard<std::mutex> lk(s->mu);
+  int save = 0;
+  (void)hipGetDevice(&save);
+  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  rc = run_write1_issue_device(s, b, o, (hipStream_t)stream);
+  (void)hipSetDevice(save);
+  return rc;
+}
+
+int mochi_signer_set_profiling(mochi_signer* s, int on) {
+  if (!s) return fail(MOCHI_EINVAL, "null signer");
+  std::lock_guard<std::mutex> lk(s->mu);
+  s->profiling = on != 0;
+  return MOCHI_OK;
+}
+
+int mochi_signer_read_issue_profile(mochi_signer* s, float* kernel_ms, uint32_t n) {
+  if (!s || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->w1_ev_valid) return fail(MOCHI_EINVAL, "no issue call was made while profiling was on");
+  static const int kSpan[mochi::kW1Stages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {6, 7}, {7, 8}, {8, 9}};
+  if (hipEventSynchronize(s->w1_ev[mochi::kW1Events - 1]) != hipSuccess)
+    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
+  for (uint32_t i = 0; i < n; i++) {
+    kernel_ms[i] = 0.f;
+    if (i < (uint32_t)mochi::kW1Stages)
+      (void)hipEventElapsedTime(&kernel_ms[i], s->w1_ev[kSpan[i][0]], s->w1_ev[kSpan[i][1]]);
+  }
+  return MOCHI_OK;
 }
 
 }  // extern "C"

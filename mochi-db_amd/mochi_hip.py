@@ -193,6 +193,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_sign_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp]
     lib.mochi_signer_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.mochi_signer_set_fault.argtypes = [vp, u32]
+    lib.mochi_write1_issue_bound.restype = ctypes.c_uint64
+    lib.mochi_write1_issue_bound.argtypes = [vp]
+    lib.mochi_write1_issue.argtypes = [vp, vp, vp]
+    lib.mochi_write1_issue_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_signer_set_profiling.argtypes = [vp, ctypes.c_int]
+    lib.mochi_signer_read_issue_profile.argtypes = [vp, vp, u32]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -1146,6 +1152,20 @@ class DeviceWrite2Source:
         self.grant_bytes_len = int(np.asarray(src.grant_bytes).size)
         self.strings_len = int(np.asarray(src.strings).size)
 
+    @classmethod
+    def from_tensors(cls, n_msgs: int, n_mgs: int, n_grants: int, n_ops: int, **tensors) -> "DeviceWrite2Source":
+        """A source whose arrays are already on the device (used as they are: no
+        copy, no host round trip), e.g. the grant_bytes / grant_off / grant_len /
+        sig a DeviceSigner.issue_device call wrote.  Every Write2Source field is a
+        torch tensor of the ABI width or None."""
+        self = cls.__new__(cls)
+        self.n_msgs, self.n_mgs, self.n_grants, self.n_ops = int(n_msgs), int(n_mgs), int(n_grants), int(n_ops)
+        for k in Write2Source.DTYPES:
+            setattr(self, k, tensors.get(k))
+        self.grant_bytes_len = int(self.grant_bytes.numel())
+        self.strings_len = int(self.strings.numel())
+        return self
+
     def to_c(self) -> Write2Source_C:
         c = Write2Source_C()
         c.n_msgs, c.n_mgs, c.n_grants, c.n_ops = self.n_msgs, self.n_mgs, self.n_grants, self.n_ops
@@ -1349,10 +1369,256 @@ class DeviceSigner:
         """Test hook: corrupt one CRT half of grant `grant_index` (-1 = off)."""
         self.lib.mochi_signer_set_fault(self.h, grant_index & 0xFFFFFFFF)
 
+    def issue_device(self, dbatch: "DeviceWrite1Batch", out: "DeviceWrite1Issued", stream: int = 0) -> int:
+        """mochi_write1_issue_device: decide, encode and (out.sig given) sign the
+        new grants of the batch, everything in device memory.  Returns the rc:
+        EINVAL when out.grant_bytes is too small (out.grant_bytes_len = the size
+        needed, out.n_new set)."""
+        b, o = dbatch.to_c(), out.to_c()
+        rc = self.lib.mochi_write1_issue_device(self.h, ctypes.addressof(b), ctypes.addressof(o), stream)
+        out.n_new, out.grant_bytes_len = int(o.n_new), int(o.grant_bytes_len)
+        if rc != OK and not (rc == EINVAL and out.grant_bytes_len > out.grant_cap):
+            raise MochiError(f"mochi_write1_issue_device rc={rc}: {_err(self.lib)}")
+        return rc
+
+    def set_profiling(self, on: bool) -> None:
+        self.lib.mochi_signer_set_profiling(self.h, 1 if on else 0)
+
+    def read_issue_profile(self) -> dict:
+        """Per-kernel device ms of the last issue_device call made while profiling was on."""
+        ms = (ctypes.c_float * len(W1_ISSUE_STAGES))()
+        if self.lib.mochi_signer_read_issue_profile(self.h, ms, len(W1_ISSUE_STAGES)) != OK:
+            raise MochiError(f"mochi_signer_read_issue_profile: {_err(self.lib)}")
+        return dict(zip(W1_ISSUE_STAGES, (float(x) for x in ms)))
+
     def close(self):
         if self.h:
             self.lib.mochi_signer_destroy(self.h)
             self.h = None
+
+
+GpuSigner = DeviceSigner
+
+# ---------------------------------------------------------------------------
+# Write1 grant issuance (InMemoryDataStore.java:105-155, :233-310): decide,
+# encode and sign the grants of a batch of Write1ToServer requests
+# ---------------------------------------------------------------------------
+W1OP_LOCAL, W1OP_HAS_SVOC, W1OP_WRITE, W1OP_DELETE = 0x01, 0x02, 0x04, 0x08
+W1_NONE, W1_STORED = 0xFFFFFFFF, 0x80000000
+W1D_SKIP, W1D_SKIPPED, W1D_FAILED, W1D_WRONG_SHARD, W1D_NEW, W1D_RETRY, W1D_REFUSED = range(7)
+W1K_OK, W1K_REFUSED, W1K_THROWS = 0, 1, 2
+W1_ISSUE_STAGES = ("k_w1_pre", "k_w1_claim", "k_w1_decide", "k_w1_reply_count", "scan", "k_w1_emit", "k_w1_reply_write",
+                   "sign")
+
+
+class Write1Batch_C(ctypes.Structure):
+    _fields_ = [("n_reqs", ctypes.c_uint32), ("n_ops", ctypes.c_uint32), ("n_stored", ctypes.c_uint32),
+                ("strings", ctypes.c_void_p), ("strings_len", ctypes.c_uint64),
+                ("req_op_off", ctypes.c_void_p), ("req_seed", ctypes.c_void_p),
+                ("req_hash_off", ctypes.c_void_p), ("req_hash_len", ctypes.c_void_p),
+                ("op_key_off", ctypes.c_void_p), ("op_key_len", ctypes.c_void_p),
+                ("op_flags", ctypes.c_void_p), ("op_obj", ctypes.c_void_p), ("op_epoch", ctypes.c_void_p),
+                ("op_stored", ctypes.c_void_p),
+                ("stored_hash_off", ctypes.c_void_p), ("stored_hash_len", ctypes.c_void_p)]
+
+
+class Write1Issued_C(ctypes.Structure):
+    _fields_ = [("op_decision", ctypes.c_void_p), ("op_grant", ctypes.c_void_p), ("req_kind", ctypes.c_void_p),
+                ("req_grant_off", ctypes.c_void_p), ("req_grant", ctypes.c_void_p),
+                ("n_new", ctypes.c_uint32), ("grant_bytes_len", ctypes.c_uint64),
+                ("grant_bytes", ctypes.c_void_p), ("grant_cap", ctypes.c_uint64),
+                ("grant_off", ctypes.c_void_p), ("grant_len", ctypes.c_void_p), ("grant_op", ctypes.c_void_p),
+                ("grant_ts", ctypes.c_void_p), ("sig", ctypes.c_void_p)]
+
+
+_W1_OUT_DTYPES = dict(op_decision=np.uint8, op_grant=np.uint32, req_kind=np.uint8, req_grant_off=np.uint32,
+                      req_grant=np.uint32, grant_off=np.uint64, grant_len=np.uint32, grant_op=np.uint32,
+                      grant_ts=np.int64)
+
+
+@dataclass
+class Write1Batch:
+    """SoA batch of Q Write1ToServer requests (mochi_write1_batch, host arrays)."""
+
+    strings: np.ndarray  # uint8: keys and hashes
+    req_op_off: np.ndarray  # uint32 [Q+1]
+    req_seed: np.ndarray  # uint32 [Q]
+    req_hash_off: np.ndarray  # uint64 [Q]
+    req_hash_len: np.ndarray  # uint32 [Q]
+    op_key_off: np.ndarray  # uint64 [O]
+    op_key_len: np.ndarray  # uint32 [O]
+    op_flags: np.ndarray  # uint8 [O] W1OP_*
+    op_obj: np.ndarray  # uint32 [O]
+    op_epoch: np.ndarray  # int64 [O]
+    op_stored: np.ndarray  # uint32 [O] stored-grant index or W1_NONE
+    stored_hash_off: np.ndarray  # uint64 [S]
+    stored_hash_len: np.ndarray  # uint32 [S]
+
+    DTYPES = dict(strings=np.uint8, req_op_off=np.uint32, req_seed=np.uint32, req_hash_off=np.uint64,
+                  req_hash_len=np.uint32, op_key_off=np.uint64, op_key_len=np.uint32, op_flags=np.uint8,
+                  op_obj=np.uint32, op_epoch=np.int64, op_stored=np.uint32, stored_hash_off=np.uint64,
+                  stored_hash_len=np.uint32)
+
+    @property
+    def n_reqs(self) -> int:
+        return int(self.req_op_off.shape[0]) - 1
+
+    @property
+    def n_ops(self) -> int:
+        return int(self.op_flags.shape[0])
+
+    @property
+    def n_stored(self) -> int:
+        return int(self.stored_hash_off.shape[0])
+
+    def arrays(self) -> dict:
+        """Every array C-contiguous in its ABI dtype."""
+        return {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write1Batch_C()
+        c.n_reqs, c.n_ops, c.n_stored = self.n_reqs, self.n_ops, self.n_stored
+        c.strings_len = int(arrs["strings"].nbytes)
+        for k, a in arrs.items():
+            if a.size == 0:  # an empty array still gets a valid address (the library reads none of it)
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+@dataclass
+class Write1Issued:
+    """Outputs of write1_issue (mochi_write1_issued), trimmed to their lengths."""
+
+    rc: int
+    op_decision: np.ndarray  # uint8 [O] W1D_*
+    op_grant: np.ndarray  # uint32 [O]
+    req_kind: np.ndarray  # uint8 [Q] W1K_*
+    req_grant_off: np.ndarray  # uint32 [Q+1]
+    req_grant: np.ndarray  # uint32
+    n_new: int
+    grant_bytes_len: int
+    grant_bytes: np.ndarray  # uint8 (the caller's buffer, whole)
+    grant_off: np.ndarray  # uint64 [n_new]
+    grant_len: np.ndarray  # uint32 [n_new]
+    grant_op: np.ndarray  # uint32 [n_new]
+    grant_ts: np.ndarray  # int64 [n_new]
+    sig: Optional[np.ndarray] = None  # uint8 [n_new, 256] (device form)
+
+    def grant(self, g: int) -> bytes:
+        o = int(self.grant_off[g])
+        return self.grant_bytes[o:o + int(self.grant_len[g])].tobytes()
+
+
+def write1_issue_bound(batch: "Write1Batch") -> int:
+    """mochi_write1_issue_bound: a safe (not tight) upper bound on the grant bytes."""
+    c, keep = batch.to_c()
+    lib = load_library()
+    return int(lib.mochi_write1_issue_bound(ctypes.addressof(c)))
+
+
+def write1_issue_into(batch: "Write1Batch", grant_bytes: Optional[np.ndarray]) -> "Write1Issued":
+    """mochi_write1_issue into the caller's buffer (uint8; None = capacity 0).
+    rc is EINVAL with grant_bytes_len = the size needed when the buffer is too
+    small (no byte of it written); any other failure raises."""
+    lib = load_library()
+    c, keep = batch.to_c()
+    Q, O = batch.n_reqs, batch.n_ops
+    n = dict(op_decision=O, op_grant=O, req_kind=Q, req_grant_off=Q + 1, req_grant=O, grant_off=O, grant_len=O,
+             grant_op=O, grant_ts=O)
+    arr = {k: np.zeros(max(n[k], 1), dt) for k, dt in _W1_OUT_DTYPES.items()}
+    o = Write1Issued_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a))
+    cap = 0 if grant_bytes is None else int(grant_bytes.nbytes)
+    o.grant_bytes, o.grant_cap = (_ptr(grant_bytes) if cap else None), cap
+    need = ctypes.c_uint64(0)
+    rc = lib.mochi_write1_issue(ctypes.addressof(c), ctypes.addressof(o), ctypes.addressof(need))
+    if rc != OK and not (rc == EINVAL and int(need.value) > cap):
+        raise MochiError(f"mochi_write1_issue rc={rc}: {_err(lib)}")
+    assert int(need.value) == int(o.grant_bytes_len)
+    nn = int(o.n_new) if rc == OK else 0
+    nr = int(arr["req_grant_off"][Q]) if rc == OK else 0
+    return Write1Issued(rc=rc, op_decision=arr["op_decision"][:O], op_grant=arr["op_grant"][:O],
+                        req_kind=arr["req_kind"][:Q], req_grant_off=arr["req_grant_off"][:Q + 1],
+                        req_grant=arr["req_grant"][:nr], n_new=int(o.n_new), grant_bytes_len=int(o.grant_bytes_len),
+                        grant_bytes=grant_bytes if cap else np.zeros(0, np.uint8), grant_off=arr["grant_off"][:nn],
+                        grant_len=arr["grant_len"][:nn], grant_op=arr["grant_op"][:nn], grant_ts=arr["grant_ts"][:nn])
+
+
+def write1_issue(batch: "Write1Batch") -> "Write1Issued":
+    """Host form of Write1 grant issuance: sizes first, then the grants into a
+    buffer of exactly the size needed."""
+    first = write1_issue_into(batch, None)
+    if first.rc == OK:  # no new grant has a byte
+        return first
+    return write1_issue_into(batch, np.zeros(first.grant_bytes_len, np.uint8))
+
+
+class DeviceWrite1Batch:
+    """A Write1Batch copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, batch: "Write1Batch", device: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: np.uint8, np.uint32: np.int32, np.uint64: np.int64, np.int64: np.int64}
+        self.n_reqs, self.n_ops, self.n_stored = batch.n_reqs, batch.n_ops, batch.n_stored
+        for k, a in batch.arrays().items():
+            if a.size == 0:
+                a = np.zeros(1, a.dtype)
+            setattr(self, k, torch.from_numpy(a.view(sv[Write1Batch.DTYPES[k]])).to(dev))
+        self.strings_len = int(np.asarray(batch.strings).size)
+
+    def to_c(self) -> Write1Batch_C:
+        c = Write1Batch_C()
+        c.n_reqs, c.n_ops, c.n_stored, c.strings_len = self.n_reqs, self.n_ops, self.n_stored, self.strings_len
+        for k in Write1Batch.DTYPES:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
+
+
+class DeviceWrite1Issued:
+    """Device buffers for the outputs of DeviceSigner.issue_device.  grant_cap
+    bytes of grant_bytes (prefilled with `fill`), sign=True adds the signature
+    rows.  n_new / grant_bytes_len are set by the call."""
+
+    def __init__(self, n_reqs: int, n_ops: int, grant_cap: int, sign: bool = False, device: int = 0, fill: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: torch.uint8, np.uint32: torch.int32, np.uint64: torch.int64, np.int64: torch.int64}
+        self.n_reqs, self.n_ops, self.grant_cap = n_reqs, n_ops, int(grant_cap)
+        n = dict(op_decision=n_ops, op_grant=n_ops, req_kind=n_reqs, req_grant_off=n_reqs + 1, req_grant=n_ops,
+                 grant_off=n_ops, grant_len=n_ops, grant_op=n_ops, grant_ts=n_ops)
+        for k, dt in _W1_OUT_DTYPES.items():
+            setattr(self, k, torch.zeros(max(n[k], 1), dtype=sv[dt], device=dev))
+        self.grant_bytes = torch.full((max(self.grant_cap, 1),), fill, dtype=torch.uint8, device=dev)
+        self.sig = torch.zeros((max(n_ops, 1), RSA_BYTES), dtype=torch.uint8, device=dev) if sign else None
+        self.n_new = 0
+        self.grant_bytes_len = 0
+
+    def to_c(self) -> Write1Issued_C:
+        o = Write1Issued_C()
+        for k in _W1_OUT_DTYPES:
+            setattr(o, k, getattr(self, k).data_ptr())
+        o.grant_bytes, o.grant_cap = self.grant_bytes.data_ptr(), self.grant_cap
+        o.sig = None if self.sig is None else self.sig.data_ptr()
+        return o
+
+    def to_host(self, rc: int = OK) -> "Write1Issued":
+        """The outputs on the host, trimmed as write1_issue trims them."""
+        Q, O = self.n_reqs, self.n_ops
+        h = {k: getattr(self, k).cpu().numpy().view(dt) for k, dt in _W1_OUT_DTYPES.items()}
+        nn = self.n_new if rc == OK else 0
+        nr = int(h["req_grant_off"][Q]) if rc == OK else 0
+        return Write1Issued(rc=rc, op_decision=h["op_decision"][:O], op_grant=h["op_grant"][:O], req_kind=h["req_kind"][:Q],
+                            req_grant_off=h["req_grant_off"][:Q + 1], req_grant=h["req_grant"][:nr], n_new=self.n_new,
+                            grant_bytes_len=self.grant_bytes_len, grant_bytes=self.grant_bytes.cpu().numpy()[:self.grant_cap],
+                            grant_off=h["grant_off"][:nn], grant_len=h["grant_len"][:nn], grant_op=h["grant_op"][:nn],
+                            grant_ts=h["grant_ts"][:nn],
+                            sig=None if self.sig is None else self.sig.cpu().numpy()[:nn])
 
 
 

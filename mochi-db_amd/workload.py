@@ -706,3 +706,82 @@ def head_certs(s: Synth, n: int) -> Synth:
                cert_op_off=b.cert_op_off[:n + 1], op_key=b.op_key[:o], op_flags=b.op_flags[:o],
                expected_hash=b.expected_hash[:n])
     return Synth(nb, s.template[:n], s.fault[:n], s.fault_replica[:n], s.expected_flags[:g])
+
+
+# ---------------------------------------------------------------------------
+# Write1 grant issuance batches (mochi_write1_batch): the requests a server's
+# Write1 handler collects in one micro-batch.  Keys are "W1_KEY_{object}" (equal
+# object <=> equal key), a container's epoch is 1000 * (object mod 64), hash id h
+# stands for the lowercase-hex SHA-512 of "w1-txn-{h}".  No per-request Python
+# loop beyond one SHA-512 per distinct hash.
+# ---------------------------------------------------------------------------
+def _w1_hash_rows(ids: np.ndarray) -> np.ndarray:
+    u, inv = np.unique(np.asarray(ids, np.int64), return_inverse=True)
+    rows = np.frombuffer(b"".join(hashlib.sha512(f"w1-txn-{int(h)}".encode()).hexdigest().encode() for h in u),
+                         np.uint8).reshape(-1, TXN_HASH_BYTES) if u.size else np.zeros((0, TXN_HASH_BYTES), np.uint8)
+    return rows[inv]
+
+
+def write1_batch(op_obj, req_op_off, req_seed, req_hash_id, op_flags=None, op_stored=None, stored_hash_id=None):
+    """The mochi_hip.Write1Batch of the given integer columns: op_obj [O] (the
+    key and the container index of each op), req_op_off [Q+1], req_seed [Q],
+    req_hash_id [Q]; op_flags defaults to LOCAL | HAS_SVOC | WRITE, op_stored to
+    "slot free"; stored_hash_id [S] names the stored grants' hashes."""
+    from mochi_hip import W1_NONE, W1OP_HAS_SVOC, W1OP_LOCAL, W1OP_WRITE, Write1Batch
+
+    op_obj = np.asarray(op_obj, np.int64)
+    n_ops, n_reqs = op_obj.shape[0], len(req_seed)
+    rows, kl = _ascii_rows(np.char.add("W1_KEY_", op_obj.astype(str)))
+    keys = rows[np.arange(rows.shape[1])[None, :] < kl[:, None]]
+    ko = np.zeros(n_ops + 1, np.int64)
+    np.cumsum(kl, out=ko[1:])
+    rh = _w1_hash_rows(req_hash_id).reshape(-1)
+    sh = _w1_hash_rows(stored_hash_id if stored_hash_id is not None else np.zeros(0, np.int64)).reshape(-1)
+    n_st = sh.size // TXN_HASH_BYTES
+    base_r, base_s = int(ko[-1]), int(ko[-1]) + rh.size
+    strings = np.concatenate([keys, rh, sh]) if base_s + sh.size else np.zeros(1, np.uint8)
+    return Write1Batch(
+        strings=strings, req_op_off=np.asarray(req_op_off, np.uint32), req_seed=np.asarray(req_seed, np.uint32),
+        req_hash_off=(base_r + TXN_HASH_BYTES * np.arange(n_reqs)).astype(np.uint64),
+        req_hash_len=np.full(n_reqs, TXN_HASH_BYTES, np.uint32),
+        op_key_off=ko[:-1].astype(np.uint64), op_key_len=kl.astype(np.uint32),
+        op_flags=(np.full(n_ops, W1OP_LOCAL | W1OP_HAS_SVOC | W1OP_WRITE, np.uint8) if op_flags is None
+                  else np.asarray(op_flags, np.uint8)),
+        op_obj=op_obj.astype(np.uint32), op_epoch=1000 * (op_obj % 64),
+        op_stored=np.full(n_ops, W1_NONE, np.uint32) if op_stored is None else np.asarray(op_stored, np.uint32),
+        stored_hash_off=(base_s + TXN_HASH_BYTES * np.arange(n_st)).astype(np.uint64),
+        stored_hash_len=np.full(n_st, TXN_HASH_BYTES, np.uint32))
+
+
+def make_write1_batch(n_reqs: int, k: int = 2, contention: float = 0.1, retry: float = 0.25, stored: float = 0.05,
+                      seed: int = SEED):
+    """n_reqs requests of k WRITE ops.  About `contention` of the ops aim at a
+    slot another op of the batch aims at too (a hot pool of objects, two to five
+    ops each, one seed); the others have a slot to themselves.  A contending
+    request repeats the hash of the slot's first request (a RETRY) with
+    probability `retry`.  `stored` of the uncontended ops meet a grant given
+    before the batch, half of those with the request's own hash."""
+    n_ops = n_reqs * k
+    oidx = np.arange(n_ops, dtype=np.uint64)
+    q_of = (oidx // np.uint64(k)).astype(np.int64)
+    hot = (_h(seed, 21, oidx) % np.uint64(10000)).astype(np.int64) < int(contention * 10000)
+    n_hot_obj = max(1, int(hot.sum()) // 3)
+    obj = np.where(hot, (_h(seed, 22, oidx) % np.uint64(n_hot_obj)).astype(np.int64), n_hot_obj + oidx.astype(np.int64))
+    # one seed for the whole batch keeps (object, seed) collisions where the objects collide
+    req_seed = np.full(n_reqs, 17, np.uint32)
+    # hashes: a request's own, or (RETRY) that of the first request on the first hot object it touches
+    hash_id = np.arange(n_reqs, dtype=np.int64)
+    first_q = np.full(n_hot_obj, n_reqs, np.int64)
+    np.minimum.at(first_q, obj[hot], q_of[hot])
+    again = hot & ((_h(seed, 23, oidx) % np.uint64(10000)).astype(np.int64) < int(retry * 10000))
+    src = np.nonzero(again)[0][::-1]  # the first such op of a request wins
+    hash_id[q_of[src]] = first_q[obj[src]]
+    hash_id = hash_id[hash_id]  # the request it copies may itself copy an earlier one (ids only go down)
+    # stored grants on slots nobody else wants
+    has = ~hot & ((_h(seed, 24, oidx) % np.uint64(10000)).astype(np.int64) < int(stored * 10000))
+    op_stored = np.full(n_ops, 0xFFFFFFFF, np.uint32)
+    op_stored[has] = np.arange(int(has.sum()), dtype=np.uint32)
+    same = (_h(seed, 25, oidx[has]) & np.uint64(1)).astype(bool)
+    stored_hash = np.where(same, hash_id[q_of[has]], n_reqs + np.arange(int(has.sum())))
+    return write1_batch(obj, np.arange(n_reqs + 1, dtype=np.int64) * k, req_seed, hash_id, op_stored=op_stored,
+                        stored_hash_id=stored_hash)
