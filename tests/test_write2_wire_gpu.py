@@ -8,6 +8,7 @@ import mochi_hip as mh
 import oracle_ffi as O
 import workload as W
 from test_write2_wire_cpu import _golden, check_decode_against_golden
+from w2_wire_corpus import _fallback_forms, _matcher_forms, _mutate, _pack
 
 pytestmark = pytest.mark.gpu
 
@@ -50,22 +51,6 @@ def _ver(pool):
     v = mh.Verifier(pool.moduli, 0)
     v.set_server_ids(W.SERVER_IDS[:pool.R])
     return v
-
-
-def _pack(msgs, pad=1):
-    off, parts, pos = [], [], 0
-    for i, m in enumerate(msgs):
-        p = (i * pad) % 4
-        parts.append(b"\x00" * p)
-        pos += p
-        off.append(pos)
-        parts.append(m)
-        pos += len(m)
-    M = len(msgs)
-    return W.WireBatch(wire=np.frombuffer(b"".join(parts) or b"\x00", np.uint8).copy(),
-                       msg_off=np.array(off, np.uint64), msg_len=np.array([len(m) for m in msgs], np.uint32),
-                       op_flags_off=None, op_flags=np.zeros(1, np.uint8),
-                       expected_hash=np.zeros((M, 128), np.uint8))
 
 
 def assert_decode_equal(a, b, what=""):
@@ -161,47 +146,6 @@ def test_wire_r7_k2(pool7k2):
         np.testing.assert_array_equal(g.cert_reason, soa.cert_reason)
         np.testing.assert_array_equal(g.cert_accept_bits, soa.cert_accept_bits)
     ver.close()
-
-
-def _mutate(rng, s, c, ids):
-    """One certificate's message with a structural mutation (decode-semantics fuzz)."""
-    b = s.batch
-    g0, g1 = int(b.cert_grant_off[c]), int(b.cert_grant_off[c + 1])
-    mgs = {}
-    for g in range(g0, g1):
-        gb = b.grant_bytes[int(b.grant_off[g]):int(b.grant_off[g]) + int(b.grant_len[g])].tobytes()
-        mgs.setdefault(int(b.signer[g]), []).append((W.grant_object_id(gb), gb, b.sig[g].tobytes()))
-    order = list(mgs)
-    kind = int(rng.integers(0, 10))
-    if kind == 1:
-        rng.shuffle(order)  # MultiGrant wire order decides g0
-    enc = []
-    for r in order:
-        items = mgs[r]
-        sigs = [(o, sg) for o, _, sg in items]
-        if kind == 2:
-            sigs = sigs[1:]  # a grant without signature
-        extra = b""
-        if kind == 3:
-            extra = b"\x48\x07" + W._ld(13, b"unknown")  # unknown fields
-        enc.append((ids[r], W.encode_multigrant([(o, gb) for o, gb, _ in items], ids[r], "cl", "", sigs) + extra))
-    if kind == 4 and len(enc) > 1:
-        enc.append((enc[0][0], enc[-1][1]))  # repeated certificate key: first place, last value
-    if kind == 5:
-        enc.insert(0, (ids[order[0]], enc[0][1]))  # duplicate of the first entry
-    ops = [W.encode_operation(2, o) for o, _, _ in mgs[order[0]]]
-    if kind == 6:
-        ops = ops + ops  # ops repeating a key (multiplicity)
-    if kind == 9:  # READ / DELETE / unknown actions, an empty operand1 -> MOCHI_OP_NOT_WRITE or not
-        ops = [W.encode_operation(int(rng.choice([0, 1, 2, 5])), o) for o, _, _ in mgs[order[0]]]
-        ops.append(W.encode_operation(2, ""))
-    m = W.encode_write2(enc, ops)
-    if kind == 7 and len(m) > 8:
-        i = int(rng.integers(0, len(m)))
-        m = m[:i] + bytes([m[i] ^ (1 << int(rng.integers(0, 8)))]) + m[i + 1:]  # random bit flip
-    if kind == 8:
-        m = m[:int(rng.integers(0, len(m) + 1))]  # truncation
-    return m
 
 
 def test_wire_fuzz_device_equals_oracle(pool4):
@@ -418,79 +362,6 @@ def test_batcher_callback_reentry(pool4):
     ver.close()
 
 
-def _fields(b):
-    """(tag, raw field bytes) of a protobuf message with varint / length-delimited fields."""
-    out, i = [], 0
-    while i < len(b):
-        j = i
-        while b[j] & 0x80:
-            j += 1
-        tag = b[i]
-        j += 1
-        if tag & 7 == 0:
-            while b[j] & 0x80:
-                j += 1
-            j += 1
-        else:
-            n, sh, k = 0, 0, j
-            while True:
-                n |= (b[k] & 0x7F) << sh
-                sh += 7
-                k += 1
-                if not b[k - 1] & 0x80:
-                    break
-            j = k + n
-        out.append((tag, b[i:j]))
-        i = j
-    return out
-
-
-def _reorder(gb):
-    """A canonical Grant with its fields written in reverse order (same parsed Grant)."""
-    return b"".join(raw for _, raw in reversed(_fields(gb)))
-
-
-def _fallback_forms(s, c, ids):
-    """Certificate c of a synthetic batch re-encoded in legal forms the device fast path
-    declines (MOCHI_MSG_FALLBACK); the library's host decoder must decide them."""
-    b = s.batch
-    g0, g1 = int(b.cert_grant_off[c]), int(b.cert_grant_off[c + 1])
-    mgs = {}
-    for g in range(g0, g1):
-        gb = b.grant_bytes[int(b.grant_off[g]):int(b.grant_off[g]) + int(b.grant_len[g])].tobytes()
-        mgs.setdefault(int(b.signer[g]), []).append((W.grant_object_id(gb), gb, b.sig[g].tobytes()))
-    ent = [(ids[r], W.encode_multigrant([(o, gb) for o, gb, _ in it], ids[r], "cl", "", [(o, sg) for o, _, sg in it]))
-           for r, it in mgs.items()]
-    ops = [W.encode_operation(2, o) for o, _, _ in next(iter(mgs.values()))]
-    canon = W.encode_write2(ent, ops)
-    wc = b"".join(W.encode_map_entry(1, k.encode(), v) for k, v in ent)
-    tx = b"".join(W._ld(1, o) for o in ops)
-    oid, gb, _ = next(iter(mgs.values()))[0]
-    forms = {
-        "canonical": canon,
-        "wc_split": W._ld(1, wc[:len(W.encode_map_entry(1, ent[0][0].encode(), ent[0][1]))]) + W._ld(2, tx) +
-                    W._ld(1, wc[len(W.encode_map_entry(1, ent[0][0].encode(), ent[0][1])):]),
-        "tx_twice": W._ld(1, wc) + W._ld(2, tx) + W._ld(2, b""),
-        # 29 extra MultiGrants from unknown servers, unsigned, same grant: 33 MultiGrants in all
-        "33_multigrants": W.encode_write2(ent + [(f"extra-{i}", W.encode_multigrant([(oid, gb)], f"extra-{i}"))
-                                                 for i in range(29)], ops),
-        # 33 certificate entries on the wire, 32 distinct keys (the first entry repeated
-        # last): the fast path counts wire entries, so this leaves it too
-        "33_entries_32_keys": W.encode_write2(ent + [(f"extra-{i}", W.encode_multigrant([(oid, gb)], f"extra-{i}"))
-                                                     for i in range(28)] + [ent[0]], ops),
-        # one MultiGrant repeating its grants / grantSignatures entries 65 times each
-        "65_grant_entries": W.encode_write2(
-            [(ids[r], W.encode_multigrant([(o, gb) for o, gb, _ in it] * 65, ids[r], "cl", "",
-                                          [(o, sg) for o, _, sg in it] * 65)) for r, it in mgs.items()], ops),
-        # every grant's fields out of canonical order: the signature covers the canonical
-        # re-encoding (Grant.toByteArray()), so it still verifies
-        "noncanonical_grants": W.encode_write2(
-            [(ids[r], W.encode_multigrant([(o, _reorder(gb)) for o, gb, _ in it], ids[r], "cl", "",
-                                          [(o, sg) for o, _, sg in it])) for r, it in mgs.items()], ops),
-    }
-    return forms
-
-
 def test_wire_fallback_messages_decided_on_host(pool4):
     """Legal messages outside the device decoder's fast path are decoded on the host
     with full protobuf-java semantics and verified on the device (signatures are never
@@ -571,88 +442,6 @@ def test_ten_byte_varint_garbage_is_not_canonical(pool4):
     assert st[0] == mh.MSG_OK and st[1] == mh.MSG_FALLBACK, st
     np.testing.assert_array_equal(g.cert_reason, o.cert_reason)
     ver.close()
-
-
-def _bad_key_byte(m, oid):
-    """m with the last byte of its first grants entry's key made 0xFF (invalid UTF-8)."""
-    kb = oid.encode()
-    pat = b"\x0a" + bytes([len(kb)]) + kb + b"\x12"
-    assert pat in m
-    return m.replace(pat, pat[:-2] + b"\xff\x12", 1)
-
-
-def _matcher_forms(s, c, ids):
-    """Certificate c re-encoded at and around the edges of k_w2_mg's layout matcher
-    (mg_match: the reference encoder's one-grant MultiGrant, ASCII key and serverId
-    <= 60 bytes, signature entry under the grant's key, Grant in its common canonical
-    shape <= 192 bytes).  Each form is legal protobuf; the matcher either decodes it
-    exactly as the walk does or leaves it to the walk."""
-    b = s.batch
-    g0, g1 = int(b.cert_grant_off[c]), int(b.cert_grant_off[c + 1])
-    items = []
-    for g in range(g0, g1):
-        gb = b.grant_bytes[int(b.grant_off[g]):int(b.grant_off[g]) + int(b.grant_len[g])].tobytes()
-        items.append((int(b.signer[g]), W.grant_object_id(gb), gb, b.sig[g].tobytes()))
-    r0, oid, gb, _ = items[0]
-    p = O.grant_parse(gb)
-    ts, th = int(p["timestamp"]), p["transaction_hash"].decode()
-    th_alt = th[:-1] + ("0" if th[-1] != "0" else "1")
-
-    def msg(grant_of=lambda r, g: g, key_of=lambda r, o: o, sig_key_of=None, sid_of=lambda r: ids[r],
-            sig_of=lambda r, sg: sg, extra_of=None, ops_of=None, cert_key_of=lambda r: ids[r], dup_entry=False):
-        ent = []
-        for r, o, g, sg in items:
-            k = key_of(r, o)
-            sk = sig_key_of(r, k) if sig_key_of else k
-            gl = grant_of(r, g)
-            grants = gl if isinstance(gl, list) else [(k, gl)]
-            mg = W.encode_multigrant(grants, sid_of(r), "", "", [(sk, sig_of(r, sg))])
-            ent.append((cert_key_of(r), mg + (extra_of(r) if extra_of else b"")))
-        if dup_entry:
-            ent.append(ent[0])  # a repeated certificate key: first position, last value
-        key = key_of(r0, oid)
-        return W.encode_write2(ent, ops_of(key) if ops_of else [W.encode_operation(2, key)])
-
-    return {
-        "plain": msg(),
-        "sig_under_other_key": msg(sig_key_of=lambda r, k: k + "x"),
-        "key_60": msg(key_of=lambda r, o: (o + "-" + "k" * 60)[:60]),
-        "key_61": msg(key_of=lambda r, o: (o + "-" + "k" * 61)[:61]),
-        "key_non_ascii": msg(key_of=lambda r, o: o + "é"),
-        "sid_non_ascii": msg(sid_of=lambda r: ids[r] + "é"),
-        "sid_61": msg(sid_of=lambda r: (ids[r] + "-" + "s" * 61)[:61]),
-        "sig_255": msg(sig_of=lambda r, sg: sg[:255]),
-        "trailing_unknown": msg(extra_of=lambda r: b"\x48\x07"),
-        "short_grant": msg(grant_of=lambda r, g: W.encode_grant(oid, ts, "ab")),
-        "grant_hash_127": msg(grant_of=lambda r, g: W.encode_grant(oid, ts, "c" * 127)),
-        "grant_hash_128": msg(grant_of=lambda r, g: W.encode_grant(oid, ts, "c" * 128)),
-        "grant_ts_1": msg(grant_of=lambda r, g: W.encode_grant(oid, 1, th)),
-        "grant_ts_9_bytes": msg(grant_of=lambda r, g: W.encode_grant(oid, 1 << 62, th)),
-        "grant_ts_negative": msg(grant_of=lambda r, g: W.encode_grant(oid, -7, th)),
-        "grant_configstamp": msg(grant_of=lambda r, g: W.encode_grant(oid, ts, th, configstamp=3)),
-        "grant_oid_non_ascii": msg(grant_of=lambda r, g: W.encode_grant(oid + "é", ts, th)),
-        "grant_hash_non_ascii": msg(grant_of=lambda r, g: W.encode_grant(oid, ts, th[:-1] + "é")),
-        "grant_reordered": msg(grant_of=lambda r, g: _reorder(g)),
-        "grant_200_bytes": msg(grant_of=lambda r, g: W.encode_grant(oid + "o" * 40, ts, th)),
-        "key_bad_utf8": _bad_key_byte(msg(), oid),
-        # level-1 shapes: operations, certificate keys
-        "op_no_action": msg(ops_of=lambda k: [W.encode_operation(0, k)]),
-        "op_operand2": msg(ops_of=lambda k: [W.encode_operation(2, k, "v")]),
-        "ops_4": msg(ops_of=lambda k: [W.encode_operation(2, k + str(i) if i else k) for i in range(4)]),
-        "ops_5": msg(ops_of=lambda k: [W.encode_operation(2, k + str(i) if i else k) for i in range(5)]),
-        "op_second_names_key": msg(ops_of=lambda k: [W.encode_operation(2, k + "z"), W.encode_operation(2, k)]),
-        "op_key_57": msg(key_of=lambda r, o: (o + "-" + "q" * 57)[:57]),
-        "cert_key_non_ascii": msg(cert_key_of=lambda r: ids[r] + "é"),
-        "cert_key_57": msg(cert_key_of=lambda r: (ids[r] + "-" + "c" * 57)[:57]),
-        "cert_key_repeated": msg(dup_entry=True),
-        "cert_keys_equal_pairs": msg(cert_key_of=lambda r: ids[r % 2]),
-        # the first MultiGrant names the grant key twice: LinkedHashMap keeps the first
-        # position and the LAST value (a variant: another transaction hash), while every
-        # other MultiGrant carries the first value's bytes -- they must not take the
-        # variant's prep results
-        "repeated_key_first_mg": msg(grant_of=lambda r, g: [(oid, g), (oid, W.encode_grant(oid, ts, th_alt))]
-                                     if r == r0 else g),
-    }
 
 
 def test_wire_layout_matcher_edges(pool4):
