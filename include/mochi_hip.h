@@ -716,6 +716,111 @@ int mochi_signer_set_profiling(mochi_signer* s, int on);
 int mochi_signer_read_issue_profile(mochi_signer* s, float* kernel_ms, uint32_t n);
 
 /* ------------------------------------------------------------------------
+ * Write1 REPLY ENCODE: the bodies the server answers a Write1 batch with
+ * (InMemoryDataStore.java:283-308, MochiProtocol.proto:117-161), one blob with
+ * msg_off / msg_len.  Request q's slice is the body of ProtocolMessage field
+ * 108 (write1OkFromServer) for req_kind OK, 109 (write1RefusedFromServer) for
+ * REFUSED and 112 (requestFailedFromServer, OLD_REQUEST: the empty body) for
+ * THROWS; the payload case is req_kind's, so no further output is needed.
+ *
+ *   Write1OkFromServer / Write1RefusedFromServer (same layout)
+ *     = 0A len MultiGrant                      always, also when empty (0A 00)
+ *       { 12 len ( 0A len objectId  12 len WriteCertificate ) }
+ *                                              per listed grant with a certificate
+ *     clientId = 3 and hash = 4 are never set by the reference: never written
+ *   MultiGrant as in mochi_write2_source: grants entries, clientId, serverId
+ *     (each iff non-empty), grantSignatures entries iff issued->sig is given.
+ *
+ * The listed grants of request q are req_grant[req_grant_off[q] ..
+ * req_grant_off[q+1]) as mochi_write1_issue wrote them; the entries of all
+ * three maps are in that order (Java's HashMap order is not reproduced).  The
+ * map key of an entry is operand1 of the first listed op of the request that
+ * refers to the grant (for a new and for a stored grant this is
+ * Grant.objectId; no grant is parsed), and its certificate is the one given
+ * for that same op.
+ *
+ * mochi_write1_reply_source is what the batch and the issue outputs do not
+ * hold already.  The server id and the client ids are slices of a blob of
+ * their own, `ids` (not of the batch's `strings`).  stored_* are the bytes and
+ * signatures of the batch's stored grants (S = batch.n_stored), read only for
+ * references MOCHI_W1_STORED | i.  op_cert_* give per op the serialized
+ * WriteCertificate of its container (getCurrentC()), opaque bytes copied as
+ * given; length 0 = no certificate = no currentCertificates entry (a non-null
+ * EMPTY certificate cannot arise: setCurrentC stores only certificates that
+ * reached quorum).  Slices of different ops may alias.  op_cert_off and
+ * op_cert_len both NULL = no certificates at all.  Signatures are written iff
+ * issued->sig is not NULL; stored_sig is then required when n_stored > 0.
+ * ------------------------------------------------------------------------ */
+typedef struct mochi_write1_reply_source {
+  const uint8_t*  ids;          uint64_t ids_len;        /* server id and client ids      */
+  uint64_t server_id_off;       uint32_t server_id_len;  /* MochiContext.getServerId()    */
+  const uint64_t* req_client_off; const uint32_t* req_client_len; /* [Q] Write1ToServer.clientId;
+                                                            both NULL = empty              */
+  const uint8_t*  stored_bytes; uint64_t stored_bytes_len;
+  const uint64_t* stored_off;   const uint32_t* stored_len; /* [S]                         */
+  const uint8_t*  stored_sig;   /* [S][256], or NULL without signatures                    */
+  const uint8_t*  certs;        uint64_t certs_len;
+  const uint64_t* op_cert_off;  const uint32_t* op_cert_len; /* [O] or both NULL            */
+} mochi_write1_reply_source;
+
+/* A safe upper bound on the wire size from counts and blob lengths alone:
+ * every op a listed grant whose key is strings_len long, whose grant is the
+ * longer of grant_bytes_len (the new grants) and stored_bytes_len, and whose
+ * certificate is certs_len long, every id ids_len long, capped by 2^31 - 1
+ * bytes per request: safe, not tight (slices may alias).  The exact size comes
+ * from the encoder called with wire_cap = 0. */
+uint64_t mochi_write1_reply_bound(uint32_t n_reqs, uint32_t n_ops, uint64_t strings_len, uint64_t ids_len,
+                                  uint64_t grant_bytes_len, uint64_t stored_bytes_len, uint64_t certs_len,
+                                  int with_signatures);
+
+/* Host form: every array in host memory, no GPU, no key; `batch` and `issued`
+ * exactly as mochi_write1_issue took and wrote them (n_new set; with a sig
+ * array the caller filled for signatures).  Messages are packed back to back;
+ * msg_off[Q], msg_len[Q] and status[Q] are always written.  status reuses
+ * mochi_enc_status: MOCHI_ENC_OK, or MOCHI_ENC_TOO_LONG for a body of 2^31
+ * bytes or more, which gets length 0.  A THROWS request gets length 0 and
+ * MOCHI_ENC_OK.  When wire_cap is smaller than the total the call returns
+ * MOCHI_EINVAL with *wire_len = the size needed and writes no byte of `wire`.
+ * MOCHI_EINVAL also for: req_op_off that is not a CSR over n_ops;
+ * req_grant_off that is not a CSR of at most n_ops references; a req_kind
+ * that is no mochi_w1_req_kind; a req_grant reference outside n_new /
+ * n_stored; a reference that no listed op of its request refers to; an id,
+ * key, grant or certificate slice outside its blob; stored_sig missing while
+ * signatures are written and n_stored > 0. */
+int mochi_write1_reply_encode(const mochi_write1_batch* batch, const mochi_write1_issued* issued,
+                              const mochi_write1_reply_source* src, uint8_t* wire, uint64_t wire_cap,
+                              uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len);
+
+/* Device form: every array of the three structs and wire / msg_off / msg_len /
+ * status in DEVICE memory, the structs themselves on the host; same bytes,
+ * offsets and statuses as the host form; the inputs are trusted.  Scratch
+ * hangs off the signer (its own, apart from the issue call's), the call takes
+ * the signer's lock and orders itself behind the signer's last call on another
+ * stream as mochi_write1_issue_device does.  It may be called on the issuing
+ * stream right after mochi_write1_issue_device with no synchronisation in
+ * between: it reads op_decision, op_grant, req_*, grant_* and sig in stream
+ * order (issued->n_new is the host field that call set).
+ *   wire_len != NULL: the call waits once for the total, applies the host
+ *     form's capacity rule on the host and returns with the emit kernels
+ *     enqueued.  Behind an issue call with sig on the same stream that wait
+ *     sits behind the signing kernels.
+ *   wire_len == NULL, wire_len_dev a device uint64_t*: no host wait.  The
+ *     total goes to *wire_len_dev; every kernel that writes `wire` reads the
+ *     total and writes nothing when it exceeds wire_cap (all or nothing, on
+ *     the device); msg_off / msg_len / status are written either way and the
+ *     call returns MOCHI_OK.  A caller that allocates
+ *     mochi_write1_reply_bound bytes never waits for a size. */
+int mochi_write1_reply_encode_device(mochi_signer* s, const mochi_write1_batch* batch,
+                                     const mochi_write1_issued* issued, const mochi_write1_reply_source* src,
+                                     uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len,
+                                     uint8_t* status, uint64_t* wire_len, uint64_t* wire_len_dev, void* stream);
+/* Per-kernel device time (ms) of the last mochi_write1_reply_encode_device call
+ * made while profiling was on (mochi_signer_set_profiling) and that emitted:
+ * [0] k_w1r_size, [1] the 64-bit scan, [2] k_w1r_hdr, [3] k_w1r_copy.  Waits
+ * for that call.  n <= 4. */
+int mochi_signer_read_reply_profile(mochi_signer* s, float* kernel_ms, uint32_t n);
+
+/* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps
  * (Write2ToServerRequestHandler.handle -> processWrite2ToServer on a 2..20
  * thread pool, MochiServer.java:36-40), coalesced across threads into one

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "mont.h"
 #include "w1_issue.h"
+#include "w1_reply.h"
 #include "w2.h"
 #include "w2_encode.h"
 #include "w2_host.h"
@@ -2070,6 +2071,12 @@ struct mochi_signer {
   hipStream_t scratch_st = nullptr;
   bool profiling = false, w1_ev_valid = false;
   std::vector<hipEvent_t> w1_ev;  // kW1Events, created on first use
+  // Write1 reply encoder (w1_reply.hip): scratch of its own, so that it can run behind an
+  // issue call whose kernels are still using w1_scratch
+  DevBuf w1r_scratch, w1r_scan;
+  PinnedBuf w1r_tot;
+  bool w1r_ev_valid = false;
+  std::vector<hipEvent_t> w1r_ev;  // kW1ReplyEvents, created on first use
 };
 
 namespace {
@@ -2201,6 +2208,7 @@ void mochi_signer_destroy(mochi_signer* s) {
   if (s->ev_tot) (void)hipEventDestroy(s->ev_tot);
   if (s->ev_scratch) (void)hipEventDestroy(s->ev_scratch);
   for (auto e : s->w1_ev) (void)hipEventDestroy(e);
+  for (auto e : s->w1r_ev) (void)hipEventDestroy(e);
   if (s->check) mochi_ctx_destroy(s->check);
   delete s;
   (void)hipSetDevice(save);
@@ -2459,6 +2467,165 @@ int mochi_signer_read_issue_profile(mochi_signer* s, float* kernel_ms, uint32_t 
     kernel_ms[i] = 0.f;
     if (i < (uint32_t)mochi::kW1Stages)
       (void)hipEventElapsedTime(&kernel_ms[i], s->w1_ev[kSpan[i][0]], s->w1_ev[kSpan[i][1]]);
+  }
+  return MOCHI_OK;
+}
+
+}  // extern "C"
+
+// ---- Write1 reply encoder (w1_reply.hip / w1_reply_host.cpp) --------------------
+namespace {
+
+int check_write1_reply(const mochi_write1_batch* b, const mochi_write1_issued* o, const mochi_write1_reply_source* s,
+                       const uint8_t* wire, uint64_t wire_cap, const uint64_t* msg_off, const uint32_t* msg_len,
+                       const uint8_t* status) {
+  if (!b || !o || !s) return fail(MOCHI_EINVAL, "null argument");
+  if (b->n_ops >= (1u << 30) || b->n_stored >= MOCHI_W1_STORED || b->n_reqs == 0xFFFFFFFFu)
+    return fail(MOCHI_EINVAL, "batch too large");
+  if (!b->req_op_off || !o->req_grant_off) return fail(MOCHI_EINVAL, "req_op_off / req_grant_off required");
+  if (b->n_reqs && (!o->req_kind || !msg_off || !msg_len || !status))
+    return fail(MOCHI_EINVAL, "req_kind / msg_off / msg_len / status required");
+  if (b->n_ops && (!b->op_key_off || !b->op_key_len || !o->op_decision || !o->op_grant || !o->req_grant))
+    return fail(MOCHI_EINVAL, "op_key_off / op_key_len / op_decision / op_grant / req_grant required");
+  if (o->n_new > b->n_ops) return fail(MOCHI_EINVAL, "n_new exceeds n_ops");
+  if (o->n_new && (!o->grant_bytes || !o->grant_off || !o->grant_len))
+    return fail(MOCHI_EINVAL, "grant_bytes / grant_off / grant_len required");
+  if (b->strings_len && !b->strings) return fail(MOCHI_EINVAL, "strings required");
+  if (s->ids_len && !s->ids) return fail(MOCHI_EINVAL, "ids required");
+  if (!s->req_client_off != !s->req_client_len) return fail(MOCHI_EINVAL, "req_client_off and req_client_len go together");
+  if (b->n_stored && (!s->stored_off || !s->stored_len || (s->stored_bytes_len && !s->stored_bytes)))
+    return fail(MOCHI_EINVAL, "stored_bytes / stored_off / stored_len required");
+  if (o->sig && b->n_stored && !s->stored_sig)
+    return fail(MOCHI_EINVAL, "stored_sig is required when signatures are written and n_stored > 0");
+  if (!s->op_cert_off != !s->op_cert_len) return fail(MOCHI_EINVAL, "op_cert_off and op_cert_len go together");
+  if (s->op_cert_off && s->certs_len && !s->certs) return fail(MOCHI_EINVAL, "certs required");
+  if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire required");
+  return MOCHI_OK;
+}
+
+int run_write1_reply_device(mochi_signer* s, const mochi_write1_batch* b, const mochi_write1_issued* o,
+                            const mochi_write1_reply_source* src, uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off,
+                            uint32_t* msg_len, uint8_t* status, uint64_t* wire_len, uint64_t* wire_len_dev,
+                            hipStream_t st) {
+  const uint32_t Q = b->n_reqs, O = b->n_ops;
+  if (wire_len) *wire_len = 0;
+  s->w1r_ev_valid = false;
+  if (Q == 0) {
+    if (!wire_len) HIP_TRY(hipMemsetAsync(wire_len_dev, 0, 8, st));
+    return MOCHI_OK;
+  }
+  int rc;
+  size_t scan_bytes = 0;
+  if (!mochi::w2_small(Q)) HIP_TRY(mochi::w1r_scan_temp_bytes(Q + 1, &scan_bytes));
+  if ((rc = s->w1r_scratch.ensure(mochi::w1r_scratch_bytes(Q, O))) || (rc = s->w1r_scan.ensure(scan_bytes)) ||
+      (rc = s->w1r_tot.ensure(8)))
+    return rc;
+  mochi::W1ReplyArgs a;
+  memset(&a, 0, sizeof a);
+  a.b = *b;
+  a.o = *o;
+  a.src = *src;
+  a.wire = wire;
+  a.wire_cap = wire_cap;
+  a.msg_off = msg_off;
+  a.msg_len = msg_len;
+  a.status = status;
+  a.scan_temp = s->w1r_scan.p;
+  a.scan_temp_bytes = s->w1r_scan.cap;
+  mochi::w1r_carve(a, s->w1r_scratch.p);
+  if (s->profiling) {
+    while (s->w1r_ev.size() < (size_t)mochi::kW1ReplyEvents) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      s->w1r_ev.push_back(e);
+    }
+    a.ev = s->w1r_ev.data();
+  }
+  // one scratch per signer: a call on another stream waits for the last call's kernels
+  // (an issue call's included: its outputs are this call's inputs)
+  if (s->scratch_used && s->scratch_st != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_scratch, 0));
+  HIP_TRY(mochi::launch_w1r_size(a, st));
+  bool fits = true;
+  uint64_t need = 0;
+  if (wire_len) {
+    uint64_t* tot = (uint64_t*)s->w1r_tot.p;
+    HIP_TRY(hipMemcpyAsync(tot, a.off64 + Q, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s->ev_tot, st));
+    HIP_TRY(hipEventSynchronize(s->ev_tot));
+    *wire_len = need = *tot;
+    fits = need <= wire_cap;
+  } else {
+    HIP_TRY(hipMemcpyAsync(wire_len_dev, a.off64 + Q, 8, hipMemcpyDeviceToDevice, st));
+  }
+  if (fits) HIP_TRY(mochi::launch_w1r_emit(a, st));
+  s->w1r_ev_valid = a.ev && fits;
+  s->scratch_used = true;
+  s->scratch_st = st;
+  HIP_TRY(hipEventRecord(s->ev_scratch, st));
+  if (!fits)
+    return fail(MOCHI_EINVAL, "wire_cap (%llu) is smaller than the encoded size (%llu)", (unsigned long long)wire_cap,
+                (unsigned long long)need);
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mochi_write1_reply_bound(uint32_t n_reqs, uint32_t n_ops, uint64_t strings_len, uint64_t ids_len,
+                                  uint64_t grant_bytes_len, uint64_t stored_bytes_len, uint64_t certs_len,
+                                  int with_signatures) {
+  // every op an entry of all three maps (its key three times), five-byte length varints throughout
+  const unsigned __int128 g = grant_bytes_len > stored_bytes_len ? grant_bytes_len : stored_bytes_len;
+  unsigned __int128 t = (unsigned __int128)n_ops * (3 * (unsigned __int128)strings_len + g + certs_len + 64 +
+                                                    (with_signatures ? MOCHI_RSA_BYTES : 0)) +
+                        (unsigned __int128)n_reqs * (2 * (unsigned __int128)ids_len + 24);
+  const unsigned __int128 cap = (unsigned __int128)n_reqs * mochi::kEncMaxMsg;  // longer bodies are emitted empty
+  if (t > cap) t = cap;
+  return (uint64_t)t;
+}
+
+int mochi_write1_reply_encode(const mochi_write1_batch* b, const mochi_write1_issued* o,
+                              const mochi_write1_reply_source* src, uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off,
+                              uint32_t* msg_len, uint8_t* status, uint64_t* wire_len) {
+  if (!wire_len) return fail(MOCHI_EINVAL, "wire_len required");
+  *wire_len = 0;
+  int rc = check_write1_reply(b, o, src, wire, wire_cap, msg_off, msg_len, status);
+  if (rc) return rc;
+  const char* err = "";
+  rc = mochi_host::write1_reply_encode(b, o, src, wire, wire_cap, msg_off, msg_len, status, wire_len, &err);
+  return rc ? fail(rc, "mochi_write1_reply_encode: %s", err) : MOCHI_OK;
+}
+
+int mochi_write1_reply_encode_device(mochi_signer* s, const mochi_write1_batch* b, const mochi_write1_issued* o,
+                                     const mochi_write1_reply_source* src, uint8_t* wire, uint64_t wire_cap,
+                                     uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                                     uint64_t* wire_len_dev, void* stream) {
+  if (!s) return fail(MOCHI_EINVAL, "null signer");
+  if (!wire_len && !wire_len_dev) return fail(MOCHI_EINVAL, "wire_len or wire_len_dev required");
+  int rc = check_write1_reply(b, o, src, wire, wire_cap, msg_off, msg_len, status);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(s->mu);
+  int save = 0;
+  (void)hipGetDevice(&save);
+  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  rc = run_write1_reply_device(s, b, o, src, wire, wire_cap, msg_off, msg_len, status, wire_len, wire_len_dev,
+                               (hipStream_t)stream);
+  (void)hipSetDevice(save);
+  return rc;
+}
+
+int mochi_signer_read_reply_profile(mochi_signer* s, float* kernel_ms, uint32_t n) {
+  if (!s || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->w1r_ev_valid) return fail(MOCHI_EINVAL, "no reply encode call was made while profiling was on");
+  static const int kSpan[mochi::kW1ReplyStages][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+  if (hipEventSynchronize(s->w1r_ev[mochi::kW1ReplyEvents - 1]) != hipSuccess)
+    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
+  for (uint32_t i = 0; i < n; i++) {
+    kernel_ms[i] = 0.f;
+    if (i < (uint32_t)mochi::kW1ReplyStages)
+      (void)hipEventElapsedTime(&kernel_ms[i], s->w1r_ev[kSpan[i][0]], s->w1r_ev[kSpan[i][1]]);
   }
   return MOCHI_OK;
 }

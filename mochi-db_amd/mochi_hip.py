@@ -199,6 +199,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_write1_issue_device.argtypes = [vp, vp, vp, vp]
     lib.mochi_signer_set_profiling.argtypes = [vp, ctypes.c_int]
     lib.mochi_signer_read_issue_profile.argtypes = [vp, vp, u32]
+    u64 = ctypes.c_uint64
+    lib.mochi_write1_reply_bound.restype = u64
+    lib.mochi_write1_reply_bound.argtypes = [u32, u32, u64, u64, u64, u64, u64, ctypes.c_int]
+    lib.mochi_write1_reply_encode.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp]
+    lib.mochi_write1_reply_encode_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.mochi_signer_read_reply_profile.argtypes = [vp, vp, u32]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -1391,6 +1397,38 @@ class DeviceSigner:
             raise MochiError(f"mochi_signer_read_issue_profile: {_err(self.lib)}")
         return dict(zip(W1_ISSUE_STAGES, (float(x) for x in ms)))
 
+    def reply_encode_device(self, dbatch: "DeviceWrite1Batch", out: "DeviceWrite1Issued",
+                            dsrc: "DeviceWrite1ReplySource", wire, msg_off, msg_len, status, stream: int = 0,
+                            wire_len_dev=None, check: bool = True):
+        """mochi_write1_reply_encode_device: the reply bodies of the batch `out`
+        was issued for, into the uint8 tensor `wire` (None = capacity 0).  May
+        follow issue_device on the same stream with no synchronisation.
+        wire_len_dev None: the call waits for the total; returns (rc, total),
+        rc EINVAL when the total exceeds the capacity (raises then if `check`).
+        wire_len_dev an int64 tensor of one element: no host wait, the total
+        goes there and nothing is written when it exceeds the capacity;
+        returns (rc, None)."""
+        b, o, s = dbatch.to_c(), out.to_c(), dsrc.to_c()
+        o.n_new, o.grant_bytes_len = out.n_new, out.grant_bytes_len
+        cap = 0 if wire is None else int(wire.numel())
+        need = ctypes.c_uint64(0)
+        rc = self.lib.mochi_write1_reply_encode_device(
+            self.h, ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(s), wire.data_ptr() if cap else None, cap,
+            msg_off.data_ptr(), msg_len.data_ptr(), status.data_ptr(),
+            ctypes.addressof(need) if wire_len_dev is None else None,
+            None if wire_len_dev is None else wire_len_dev.data_ptr(), stream)
+        short = wire_len_dev is None and rc == EINVAL and int(need.value) > cap
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_write1_reply_encode_device rc={rc}: {_err(self.lib)}")
+        return rc, (int(need.value) if wire_len_dev is None else None)
+
+    def read_reply_profile(self) -> dict:
+        """Per-kernel device ms of the last reply_encode_device call made while profiling was on."""
+        ms = (ctypes.c_float * len(W1_REPLY_STAGES))()
+        if self.lib.mochi_signer_read_reply_profile(self.h, ms, len(W1_REPLY_STAGES)) != OK:
+            raise MochiError(f"mochi_signer_read_reply_profile: {_err(self.lib)}")
+        return dict(zip(W1_REPLY_STAGES, (float(x) for x in ms)))
+
     def close(self):
         if self.h:
             self.lib.mochi_signer_destroy(self.h)
@@ -1619,6 +1657,164 @@ class DeviceWrite1Issued:
                             grant_off=h["grant_off"][:nn], grant_len=h["grant_len"][:nn], grant_op=h["grant_op"][:nn],
                             grant_ts=h["grant_ts"][:nn],
                             sig=None if self.sig is None else self.sig.cpu().numpy()[:nn])
+
+
+# ---------------------------------------------------------------------------
+# Write1 reply bodies (InMemoryDataStore.java:283-308): Write1OkFromServer /
+# Write1RefusedFromServer from the issue outputs, one blob with offsets
+# ---------------------------------------------------------------------------
+W1_REPLY_STAGES = ("k_w1r_size", "scan", "k_w1r_hdr", "k_w1r_copy")
+
+
+class Write1ReplySource_C(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("ids_len", ctypes.c_uint64),
+                ("server_id_off", ctypes.c_uint64), ("server_id_len", ctypes.c_uint32),
+                ("req_client_off", ctypes.c_void_p), ("req_client_len", ctypes.c_void_p),
+                ("stored_bytes", ctypes.c_void_p), ("stored_bytes_len", ctypes.c_uint64),
+                ("stored_off", ctypes.c_void_p), ("stored_len", ctypes.c_void_p), ("stored_sig", ctypes.c_void_p),
+                ("certs", ctypes.c_void_p), ("certs_len", ctypes.c_uint64),
+                ("op_cert_off", ctypes.c_void_p), ("op_cert_len", ctypes.c_void_p)]
+
+
+@dataclass
+class Write1ReplySource:
+    """What a Write1 reply needs beyond the batch and the issue outputs
+    (mochi_write1_reply_source, host arrays)."""
+
+    ids: np.ndarray  # uint8: the server id and the client ids
+    server_id_off: int
+    server_id_len: int
+    req_client_off: Optional[np.ndarray]  # uint64 [Q] or None = no client ids
+    req_client_len: Optional[np.ndarray]  # uint32 [Q]
+    stored_bytes: np.ndarray  # uint8: the batch's stored grants
+    stored_off: np.ndarray  # uint64 [S]
+    stored_len: np.ndarray  # uint32 [S]
+    stored_sig: Optional[np.ndarray]  # uint8 [S, 256] or None
+    certs: np.ndarray  # uint8: serialized WriteCertificates
+    op_cert_off: Optional[np.ndarray]  # uint64 [O] or None = no certificates
+    op_cert_len: Optional[np.ndarray]  # uint32 [O] (0 = none for this op)
+
+    DTYPES = dict(ids=np.uint8, req_client_off=np.uint64, req_client_len=np.uint32, stored_bytes=np.uint8,
+                  stored_off=np.uint64, stored_len=np.uint32, stored_sig=np.uint8, certs=np.uint8,
+                  op_cert_off=np.uint64, op_cert_len=np.uint32)
+
+    def arrays(self) -> dict:
+        """Every given array C-contiguous in its ABI dtype (None stays None)."""
+        return {k: None if getattr(self, k) is None else np.ascontiguousarray(getattr(self, k), dt).reshape(-1)
+                for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write1ReplySource_C()
+        c.server_id_off, c.server_id_len = int(self.server_id_off), int(self.server_id_len)
+        c.ids_len, c.stored_bytes_len, c.certs_len = (int(arrs[k].size) for k in ("ids", "stored_bytes", "certs"))
+        for k, a in arrs.items():
+            if a is not None and a.size == 0:  # an empty array still gets a valid address
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def _issued_c(issued: "Write1Issued"):
+    """mochi_write1_issued over the host arrays of a Write1Issued (reply encoder input)."""
+    o = Write1Issued_C()
+    keep = {}
+    for k, dt in _W1_OUT_DTYPES.items():
+        a = np.ascontiguousarray(getattr(issued, k), dt).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1, dt)
+        setattr(o, k, _ptr(keep[k]))
+    gb = np.ascontiguousarray(issued.grant_bytes, np.uint8).reshape(-1)
+    keep["grant_bytes"] = gb if gb.size else np.zeros(1, np.uint8)
+    o.grant_bytes, o.grant_cap = _ptr(keep["grant_bytes"]), int(gb.size)
+    o.n_new, o.grant_bytes_len = int(issued.n_new), int(issued.grant_bytes_len)
+    if issued.sig is not None:
+        sg = np.ascontiguousarray(issued.sig, np.uint8).reshape(-1)
+        keep["sig"] = sg if sg.size else np.zeros(RSA_BYTES, np.uint8)
+        o.sig = _ptr(keep["sig"])
+    return o, keep
+
+
+def write1_reply_bound(batch, src, grant_bytes_len: int, with_signatures: bool) -> int:
+    """mochi_write1_reply_bound: a safe (not tight) upper bound on the reply bytes
+    of a batch whose new grants take at most grant_bytes_len bytes (after the
+    issue call its grant_bytes_len; before it, write1_issue_bound).  `batch` and
+    `src` may be the host or the device classes."""
+    lib = load_library()
+    size = lambda o, k: int(getattr(o, k + "_len")) if hasattr(o, k + "_len") else int(np.asarray(getattr(o, k)).size)
+    return int(lib.mochi_write1_reply_bound(
+        batch.n_reqs, batch.n_ops, size(batch, "strings"), size(src, "ids"), int(grant_bytes_len),
+        size(src, "stored_bytes"), size(src, "certs") if src.op_cert_off is not None else 0, 1 if with_signatures else 0))
+
+
+def write1_reply_encode_into(batch: "Write1Batch", issued: "Write1Issued", src: "Write1ReplySource",
+                             wire: Optional[np.ndarray]):
+    """mochi_write1_reply_encode into the caller's buffer (uint8; None = capacity
+    0).  Returns (rc, wire_len, msg_off, msg_len, status); rc is EINVAL with
+    wire_len = the size needed when the buffer is too small (no byte of it
+    written); any other failure raises."""
+    lib = load_library()
+    b, keep_b = batch.to_c()
+    o, keep_o = _issued_c(issued)
+    s, keep_s = src.to_c()
+    Q = batch.n_reqs
+    off, ln, st = np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint8)
+    cap = 0 if wire is None else int(wire.nbytes)
+    need = ctypes.c_uint64(0)
+    rc = lib.mochi_write1_reply_encode(ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(s),
+                                       _ptr(wire) if cap else None, cap, _ptr(off), _ptr(ln), _ptr(st),
+                                       ctypes.addressof(need))
+    if rc != OK and not (rc == EINVAL and int(need.value) > cap):
+        raise MochiError(f"mochi_write1_reply_encode rc={rc}: {_err(lib)}")
+    return rc, int(need.value), off[:Q], ln[:Q], st[:Q]
+
+
+def write1_reply_encode(batch: "Write1Batch", issued: "Write1Issued", src: "Write1ReplySource"):
+    """Host form of the Write1 reply encoder: sizes first, then the bodies into
+    a buffer of exactly the size needed.  Returns (wire, msg_off, msg_len, status)."""
+    rc, need, off, ln, st = write1_reply_encode_into(batch, issued, src, None)
+    wire = np.zeros(need, np.uint8)
+    if need:
+        rc, need, off, ln, st = write1_reply_encode_into(batch, issued, src, wire)
+    assert rc == OK
+    return wire, off, ln, st
+
+
+class DeviceWrite1ReplySource:
+    """A Write1ReplySource copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, src: "Write1ReplySource", device: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: np.uint8, np.uint32: np.int32, np.uint64: np.int64}
+        self.server_id_off, self.server_id_len = int(src.server_id_off), int(src.server_id_len)
+        for k, a in src.arrays().items():
+            if a is not None:
+                if k in ("ids", "stored_bytes", "certs"):
+                    setattr(self, k + "_len", int(a.size))
+                a = torch.from_numpy((a if a.size else np.zeros(1, a.dtype)).view(sv[Write1ReplySource.DTYPES[k]])).to(dev)
+            setattr(self, k, a)
+
+    @classmethod
+    def from_tensors(cls, server_id_off: int, server_id_len: int, **tensors) -> "DeviceWrite1ReplySource":
+        """Arrays already on the device (uint64 as int64, uint32 as int32); absent = None."""
+        self = cls.__new__(cls)
+        self.server_id_off, self.server_id_len = int(server_id_off), int(server_id_len)
+        for k in Write1ReplySource.DTYPES:
+            t = tensors.get(k)
+            setattr(self, k, t)
+            if k in ("ids", "stored_bytes", "certs"):
+                setattr(self, k + "_len", 0 if t is None else int(t.numel()))
+        return self
+
+    def to_c(self) -> Write1ReplySource_C:
+        c = Write1ReplySource_C()
+        c.server_id_off, c.server_id_len = self.server_id_off, self.server_id_len
+        c.ids_len, c.stored_bytes_len, c.certs_len = self.ids_len, self.stored_bytes_len, self.certs_len
+        for k in Write1ReplySource.DTYPES:
+            t = getattr(self, k)
+            setattr(c, k, None if t is None else t.data_ptr())
+        return c
 
 
 
