@@ -336,6 +336,17 @@ int mochi_pem_modulus(const char* pem_key, uint8_t* n_be_out);
  * (MochiDBClient.java:166,373) or -1.  reason[r]: 0 accept, 1 op-count
  * mismatch (InconsistentRead/WriteException at :159-161 / :366-368), 2 below
  * majority (:171-175 / :378-381).  Host memory; pure CPU.
+ *
+ * Arguments (host and device form alike): an argument nobody reads is not
+ * required.  chosen and reason are optional outputs (NULL = not wanted);
+ * chosen_off is read only when chosen is given and may be NULL otherwise.
+ * With n_requests == 0 every pointer may be NULL and nothing is written.
+ * Every other pointer must be non-NULL (MOCHI_EINVAL).  chosen_off and
+ * status_off need not be ascending or dense, and responses may share a
+ * status slice.  Every word of accept_bits[ceil(n_requests/32)] is written,
+ * the bits past n_requests in the last word as 0; for every request all
+ * n_ops[r] entries of chosen are written whatever the reason, and nothing
+ * else is.
  */
 int mochi_tally_responses(uint32_t n_requests, const uint32_t* resp_off, const uint32_t* n_ops,
                           const uint32_t* resp_n_ops, const uint64_t* status_off, const uint8_t* status,
@@ -383,7 +394,17 @@ enum mochi_write1_decision {
 int mochi_write1_classify(uint32_t n_requests, const uint32_t* resp_off, const uint8_t* resp_kind,
                           const uint32_t* resp_server, const uint32_t* resp_grant_off, const uint8_t* grant_key,
                           const int64_t* grant_ts, const uint8_t* grant_status, uint8_t* decision);
-/* The Write1 classification on the device (device pointers, async on `stream`). */
+/* The Write1 classification on the device (device pointers, async on `stream`).
+ *
+ * Arguments (host and device form alike): with n_requests == 0 every pointer
+ * may be NULL and nothing is written; otherwise resp_off, resp_kind,
+ * resp_server, resp_grant_off and decision must be non-NULL (MOCHI_EINVAL).
+ * grant_key / grant_ts / grant_status are read only where a response has
+ * grants and may be NULL when none has.  The host form checks that
+ * (MOCHI_EINVAL for NULL grant arrays when resp_grant_off spans a grant); the
+ * device form cannot validate the grant arrays against resp_grant_off, which
+ * lives in device memory: passing NULL grant arrays with a resp_grant_off that
+ * spans grants is undefined there. */
 int mochi_write1_classify_device(uint32_t n_requests, const uint32_t* resp_off, const uint8_t* resp_kind,
                                  const uint32_t* resp_server, const uint32_t* resp_grant_off, const uint8_t* grant_key,
                                  const int64_t* grant_ts, const uint8_t* grant_status, uint8_t* decision,

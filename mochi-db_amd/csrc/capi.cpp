@@ -1961,7 +1961,9 @@ int mochi_tally_responses(uint32_t n_requests, const uint32_t* resp_off, const u
                           const uint32_t* resp_n_ops, const uint64_t* status_off, const uint8_t* status,
                           const uint64_t* chosen_off, uint32_t replication_factor, int32_t* chosen, uint8_t* reason,
                           uint32_t* accept_bits) {
-  if (!resp_off || !n_ops || !resp_n_ops || !status_off || !status || !chosen_off || !accept_bits)
+  // the device form's rule: an argument nobody reads is not required
+  if (!n_requests) return MOCHI_OK;
+  if (!resp_off || !n_ops || !resp_n_ops || !status_off || !status || !accept_bits || (chosen && !chosen_off))
     return fail(MOCHI_EINVAL, "null argument");
   const uint32_t M = 2 * (replication_factor / 3) + 1;  // getServerMajority
   memset(accept_bits, 0, ((size_t)n_requests + 31) / 32 * 4);
@@ -1996,6 +1998,7 @@ int mochi_tally_responses(uint32_t n_requests, const uint32_t* resp_off, const u
 int mochi_write1_classify(uint32_t n_requests, const uint32_t* resp_off, const uint8_t* resp_kind,
                           const uint32_t* resp_server, const uint32_t* resp_grant_off, const uint8_t* grant_key,
                           const int64_t* grant_ts, const uint8_t* grant_status, uint8_t* decision) {
+  if (!n_requests) return MOCHI_OK;
   if (!resp_off || !resp_kind || !resp_server || !resp_grant_off || !decision)
     return fail(MOCHI_EINVAL, "null argument");
   if (resp_grant_off[resp_off[n_requests]] > resp_grant_off[0] && (!grant_key || !grant_ts || !grant_status))
