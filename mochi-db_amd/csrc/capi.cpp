@@ -120,6 +120,102 @@ struct PinnedBuf {
   }
 };
 
+// What one wire encoder (w2_encode.hip, w1_issue.hip, w1_reply.hip) keeps between calls.
+struct EncState {
+  DevBuf scratch, scan;        // per-call scratch; temp of the device-wide scan
+  PinnedBuf tot;               // the totals the host waits for
+  std::vector<hipEvent_t> ev;  // per-kernel events of the last call made while profiling, created on first use
+  bool ev_valid = false;       // ev holds a whole call: read_profile may read it
+  // scan_n: elements of the device-wide 64-bit scan, 0 on the single-block path (no temp)
+  int prepare(size_t scratch_bytes, uint32_t scan_n, size_t tot_bytes) {
+    size_t scan_bytes = 0;
+    if (scan_n) HIP_TRY(mochi::enc_scan_temp_bytes(scan_n, &scan_bytes));
+    int rc;
+    if ((rc = scratch.ensure(scratch_bytes)) || (rc = scan.ensure(scan_bytes))) return rc;
+    return tot.ensure(tot_bytes);
+  }
+  // *out = n events to stamp while profiling, null otherwise
+  int events(bool profiling, int n, hipEvent_t** out) {
+    ev_valid = false;
+    *out = nullptr;
+    while (profiling && ev.size() < (size_t)n) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+    if (profiling) *out = ev.data();
+    return MOCHI_OK;
+  }
+  // all a call needs before its first launch: the buffers, a's scratch pointers through the
+  // encoder's one layout function, its scan temp and its events
+  template <class Args>
+  int begin(Args& a, size_t (*layout)(Args&, void*), uint32_t scan_n, size_t tot_bytes, bool profiling, int n_ev) {
+    int rc;
+    if ((rc = prepare(layout(a, nullptr), scan_n, tot_bytes)) || (rc = events(profiling, n_ev, &a.ev))) return rc;
+    a.scan_temp = scan.p;
+    a.scan_temp_bytes = scan.cap;
+    layout(a, scratch.p);
+    return MOCHI_OK;
+  }
+  // the totals the size phase left at `dev`, in tot.p once this returns
+  int fetch_totals(const void* dev, size_t bytes, hipEvent_t ev_tot, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(tot.p, dev, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev_tot, st));
+    HIP_TRY(hipEventSynchronize(ev_tot));
+    return MOCHI_OK;
+  }
+  // kernel_ms[i] = time between events span[i][0] and span[i][1] of the last profiled call
+  int read_profile(const int (*span)[2], int n_stages, float* kernel_ms, uint32_t n, const char* none_msg) {
+    if (!ev_valid) return fail(MOCHI_EINVAL, "%s", none_msg);
+    if (hipEventSynchronize(ev.back()) != hipSuccess) return fail(MOCHI_EHIP, "hipEventSynchronize failed");
+    for (uint32_t i = 0; i < n; i++) {
+      kernel_ms[i] = 0.f;
+      if (i < (uint32_t)n_stages) (void)hipEventElapsedTime(&kernel_ms[i], ev[span[i][0]], ev[span[i][1]]);
+    }
+    return MOCHI_OK;
+  }
+  ~EncState() {
+    for (auto e : ev) (void)hipEventDestroy(e);
+  }
+};
+
+// Scratch ordering across calls and streams: every launch that uses its owner's scratch
+// waits for the previous one to be done with it (the device entry points are async on a
+// caller-chosen stream, so two calls on different streams would otherwise race on it).
+struct ScratchOrder {
+  hipEvent_t ev = nullptr;  // created and destroyed by the owner
+  bool used = false;
+  hipStream_t st = nullptr;  // the stream ev was last recorded on
+  hipError_t acquire(hipStream_t s) {
+    // on the stream that last released the scratch, stream order already holds
+    // (a wait there is one more API call and barrier packet per small batch)
+    return used && st != s ? hipStreamWaitEvent(s, ev, 0) : hipSuccess;
+  }
+  hipError_t release(hipStream_t s) {
+    used = true;
+    st = s;
+    return hipEventRecord(ev, s);
+  }
+};
+
+// the device of a context or signer for one call; the caller's device again on return
+struct DeviceGuard {
+  int save = 0;
+  bool ok;
+  explicit DeviceGuard(int device) {
+    (void)hipGetDevice(&save);
+    ok = hipSetDevice(device) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (ok) (void)hipSetDevice(save);
+  }
+};
+
+int capacity_error(const char* cap_name, uint64_t cap, const char* need_name, uint64_t need) {
+  return fail(MOCHI_EINVAL, "%s (%llu) is smaller than the %s (%llu)", cap_name, (unsigned long long)cap, need_name,
+              (unsigned long long)need);
+}
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- host-side key precompute (OpenSSL BN, setup only) --------------------
@@ -291,13 +387,7 @@ struct mochi_ctx {
   hipStream_t s_in = nullptr, s_out = nullptr;  // host-path copy streams
   hipStream_t aux = nullptr;                     // grant prep (high priority), beside k_rsa_pow
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // Scratch ordering: every launch that uses the context's scratch waits for
-  // the previous one to be done with it (the device entry points are async on a
-  // caller-chosen stream, so two calls on different streams would otherwise
-  // race on digest / perm / xbuf / decode buffers).
-  hipEvent_t ev_scratch = nullptr;
-  bool scratch_used = false;
-  hipStream_t scratch_st = nullptr;  // the stream ev_scratch was last recorded on
+  ScratchOrder order;  // over digest / perm / xbuf / the decode and encode buffers
   std::vector<hipEvent_t> chunk_ev;              // host-path chunk hand-offs
   std::vector<hipEvent_t> tot_ev;                // wire host path: per-chunk decode totals on the host
   // two sets of the host-path call's span events: a call records into one while
@@ -318,11 +408,7 @@ struct mochi_ctx {
       w2_mgo, w2_ots, w2_okoff, w2_oklen, w2_same;
   PinnedBuf w2_tot;
   hipEvent_t ev_tot = nullptr;
-  // Write2 encoder (w2_encode.hip): per-batch scratch, scan temp, the wire size on the host
-  DevBuf w2e_scratch, w2e_scan;
-  PinnedBuf w2e_tot;
-  std::vector<hipEvent_t> w2e_ev;  // per-kernel events of the last encode call made while profiling
-  bool w2e_ev_valid = false;
+  EncState w2e;  // Write2 encoder (w2_encode.hip); its total is the wire size
   // the last host-path call's certificate accept bitmap on the device (a slice
   // of dev_out, valid until the next call on this context; nullptr when the
   // device copy is not the final verdict, e.g. after host fallback decisions):
@@ -449,7 +535,7 @@ mochi_ctx* mochi_ctx_create(int device, const uint8_t* moduli_be, uint32_t n_key
             create_prep_stream(&c->aux) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&c->ev_scratch, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->order.ev, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_tot, hipEventDisableTiming) == hipSuccess &&
             hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking) == hipSuccess &&
             hipMalloc(&c->d_keys, sizeof(mochi::KeyEntry) * n_keys) == hipSuccess &&
@@ -497,9 +583,8 @@ void mochi::ctx_free(mochi_ctx* c) {
   if (c->aux) (void)hipStreamDestroy(c->aux);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
+  if (c->order.ev) (void)hipEventDestroy(c->order.ev);
   if (c->ev_tot) (void)hipEventDestroy(c->ev_tot);
-  for (auto e : c->w2e_ev) (void)hipEventDestroy(e);
   if (c->s_out) (void)hipStreamDestroy(c->s_out);
   if (c->d_keys) (void)hipFree(c->d_keys);
   if (c->d_fold) (void)hipFree(c->d_fold);
@@ -577,17 +662,9 @@ void resolve_timing(mochi_ctx* c) {
   (void)hipEventElapsedTime(&c->last_total_ms, e[0], e[3]);
 }
 
-// Scratch ordering across calls and streams (see mochi_ctx::ev_scratch).
-hipError_t scratch_acquire(mochi_ctx* c, hipStream_t st) {
-  // on the stream that last released the scratch, stream order already holds
-  // (a wait there is one more API call and barrier packet per small batch)
-  return c->scratch_used && c->scratch_st != st ? hipStreamWaitEvent(st, c->ev_scratch, 0) : hipSuccess;
-}
-hipError_t scratch_release(mochi_ctx* c, hipStream_t st) {
-  c->scratch_used = true;
-  c->scratch_st = st;
-  return hipEventRecord(c->ev_scratch, st);
-}
+// Scratch ordering across calls and streams (ScratchOrder).
+hipError_t scratch_acquire(mochi_ctx* c, hipStream_t st) { return c->order.acquire(st); }
+hipError_t scratch_release(mochi_ctx* c, hipStream_t st) { return c->order.release(st); }
 
 int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C);
 
@@ -1309,13 +1386,9 @@ int run_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8_t
                              hipStream_t st) {
   if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
   *wire_len = 0;
-  if (s->n_msgs == 0) return MOCHI_OK;
-  int rc;
-  size_t scan_bytes = 0;
-  if (!mochi::w2_small(s->n_msgs)) HIP_TRY(mochi::w2_enc_scan_temp_bytes(s->n_msgs + 1, &scan_bytes));
-  if ((rc = c->w2e_scratch.ensure(mochi::w2_enc_scratch_bytes(s->n_msgs, s->n_mgs, s->n_grants))) ||
-      (rc = c->w2e_scan.ensure(scan_bytes)) || (rc = c->w2e_tot.ensure(8)))
-    return rc;
+  const uint32_t M = s->n_msgs;
+  if (M == 0) return MOCHI_OK;
+  EncState& x = c->w2e;
   mochi::W2EncArgs a;
   memset(&a, 0, sizeof a);
   a.src = *s;
@@ -1326,32 +1399,17 @@ int run_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8_t
   a.msg_off = msg_off;
   a.msg_len = msg_len;
   a.status = status;
-  a.scan_temp = c->w2e_scan.p;
-  a.scan_temp_bytes = c->w2e_scan.cap;
-  mochi::w2_enc_carve(a, c->w2e_scratch.p);
-  c->w2e_ev_valid = false;
-  if (c->profiling) {
-    while (c->w2e_ev.size() < (size_t)mochi::kW2EncEvents) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->w2e_ev.push_back(e);
-    }
-    a.ev = c->w2e_ev.data();
-  }
-  HIP_TRY(scratch_acquire(c, st));
+  int rc = x.begin(a, mochi::w2_enc_layout, mochi::w2_small(M) ? 0 : M + 1, 8, c->profiling, mochi::kW2EncEvents);
+  if (rc) return rc;
+  HIP_TRY(c->order.acquire(st));
   HIP_TRY(mochi::launch_w2_enc_size(a, st));
-  uint64_t* tot = (uint64_t*)c->w2e_tot.p;
-  HIP_TRY(hipMemcpyAsync(tot, a.off64 + s->n_msgs, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipEventRecord(c->ev_tot, st));
-  HIP_TRY(hipEventSynchronize(c->ev_tot));
-  *wire_len = *tot;
-  if (*tot <= wire_cap) HIP_TRY(mochi::launch_w2_enc_emit(a, st));
-  c->w2e_ev_valid = a.ev && *tot <= wire_cap;
-  HIP_TRY(scratch_release(c, st));
-  if (*tot > wire_cap)
-    return fail(MOCHI_EINVAL, "wire_cap (%llu) is smaller than the encoded size (%llu)", (unsigned long long)wire_cap,
-                (unsigned long long)*tot);
-  return MOCHI_OK;
+  if ((rc = x.fetch_totals(a.off64 + M, 8, c->ev_tot, st))) return rc;
+  const uint64_t need = *wire_len = *(const uint64_t*)x.tot.p;
+  const bool fits = need <= wire_cap;
+  if (fits) HIP_TRY(mochi::launch_w2_enc_emit(a, st));
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(c->order.release(st));
+  return fits ? MOCHI_OK : capacity_error("wire_cap", wire_cap, "encoded size", need);
 }
 
 }  // namespace
@@ -1391,13 +1449,10 @@ int mochi_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8
   if (rc) return rc;
   if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire required");
   std::lock_guard<std::mutex> lk(c->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   new_call(c);
-  rc = run_write2_encode_device(c, s, wire, wire_cap, msg_off, msg_len, status, wire_len, (hipStream_t)stream);
-  (void)hipSetDevice(save);
-  return rc;
+  return run_write2_encode_device(c, s, wire, wire_cap, msg_off, msg_len, status, wire_len, (hipStream_t)stream);
 }
 
 // ---- Write2 wire path: the messages the device decoder declines -------------
@@ -1936,15 +1991,9 @@ int mochi_ctx_read_profile(mochi_ctx* c, float* stage_ms, uint32_t n_stages, uin
 int mochi_ctx_read_encode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n_kernels) {
   if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->w2e_ev_valid) return fail(MOCHI_EINVAL, "no encode call was made while profiling was on");
   static const int kSpan[mochi::kW2EncStages][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}, {5, 6}, {6, 7}};
-  if (hipEventSynchronize(c->w2e_ev[mochi::kW2EncEvents - 1]) != hipSuccess)
-    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
-  for (uint32_t i = 0; i < n_kernels; i++) {
-    kernel_ms[i] = 0.f;
-    if (i < (uint32_t)mochi::kW2EncStages) (void)hipEventElapsedTime(&kernel_ms[i], c->w2e_ev[kSpan[i][0]], c->w2e_ev[kSpan[i][1]]);
-  }
-  return MOCHI_OK;
+  return c->w2e.read_profile(kSpan, mochi::kW2EncStages, kernel_ms, n_kernels,
+                             "no encode call was made while profiling was on");
 }
 
 int mochi_ctx_last_timing(mochi_ctx* c, float* h2d_ms, float* kernels_ms, float* d2h_ms) {
@@ -2066,20 +2115,13 @@ struct mochi_signer {
   mochi_ctx* check = nullptr;
   DevBuf zeros, flags, misc;  // signer index / key slot zeros, SIG_OK flags, [0] rejected [1..] CSR zeros
   uint32_t fault_idx = 0xFFFFFFFFu;
-  // Write1 issuance (w1_issue.hip): per-call scratch, scan temp, the two totals on the host
-  DevBuf w1_scratch, w1_scan;
-  PinnedBuf w1_tot;
-  hipEvent_t ev_tot = nullptr, ev_scratch = nullptr;  // totals landed; last user of the scratch done
-  bool scratch_used = false;
-  hipStream_t scratch_st = nullptr;
-  bool profiling = false, w1_ev_valid = false;
-  std::vector<hipEvent_t> w1_ev;  // kW1Events, created on first use
+  EncState w1;  // Write1 issuance (w1_issue.hip); its totals are n_new and the grant bytes
   // Write1 reply encoder (w1_reply.hip): scratch of its own, so that it can run behind an
-  // issue call whose kernels are still using w1_scratch
-  DevBuf w1r_scratch, w1r_scan;
-  PinnedBuf w1r_tot;
-  bool w1r_ev_valid = false;
-  std::vector<hipEvent_t> w1r_ev;  // kW1ReplyEvents, created on first use
+  // issue call whose kernels are still using w1.scratch
+  EncState w1r;
+  hipEvent_t ev_tot = nullptr;  // totals landed
+  ScratchOrder order;           // one for both encoders
+  bool profiling = false;
 };
 
 namespace {
@@ -2172,7 +2214,7 @@ mochi_signer* mochi_signer_create(int device, const char* pem) {
   (void)hipGetDevice(&save);
   ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
        hipEventCreateWithFlags(&s->ev_tot, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&s->ev_scratch, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&s->order.ev, hipEventDisableTiming) == hipSuccess &&
        hipMalloc(&s->d_key, host.size()) == hipSuccess &&
        hipMemcpy(s->d_key, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
   memset(host.data(), 0, host.size());
@@ -2209,9 +2251,7 @@ void mochi_signer_destroy(mochi_signer* s) {
   }
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (s->ev_tot) (void)hipEventDestroy(s->ev_tot);
-  if (s->ev_scratch) (void)hipEventDestroy(s->ev_scratch);
-  for (auto e : s->w1_ev) (void)hipEventDestroy(e);
-  for (auto e : s->w1r_ev) (void)hipEventDestroy(e);
+  if (s->order.ev) (void)hipEventDestroy(s->order.ev);
   if (s->check) mochi_ctx_destroy(s->check);
   delete s;
   (void)hipSetDevice(save);
@@ -2361,36 +2401,20 @@ int check_write1(const mochi_write1_batch* b, const mochi_write1_issued* o) {
 
 int run_write1_issue_device(mochi_signer* s, const mochi_write1_batch* b, mochi_write1_issued* o, hipStream_t st) {
   const uint32_t Q = b->n_reqs, O = b->n_ops;
-  int rc;
-  size_t scan_bytes = 0;
-  if (!(mochi::w2_small(O) && mochi::w2_small(Q))) HIP_TRY(mochi::w1_scan_temp_bytes((O > Q ? O : Q) + 1, &scan_bytes));
-  if ((rc = s->w1_scratch.ensure(mochi::w1_scratch_bytes(Q, O))) || (rc = s->w1_scan.ensure(scan_bytes)) ||
-      (rc = s->w1_tot.ensure(16)))
-    return rc;
+  EncState& x = s->w1;
   mochi::W1Args a;
   memset(&a, 0, sizeof a);
   a.b = *b;
   a.o = *o;
   a.slots = (uint32_t)mochi::w1_table_slots(O);
-  a.scan_temp = s->w1_scan.p;
-  a.scan_temp_bytes = s->w1_scan.cap;
-  mochi::w1_carve(a, s->w1_scratch.p);
-  s->w1_ev_valid = false;
-  if (s->profiling) {
-    while (s->w1_ev.size() < (size_t)mochi::kW1Events) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      s->w1_ev.push_back(e);
-    }
-    a.ev = s->w1_ev.data();
-  }
+  const uint32_t scan_n = mochi::w2_small(O) && mochi::w2_small(Q) ? 0 : (O > Q ? O : Q) + 1;
+  int rc = x.begin(a, mochi::w1_layout, scan_n, 16, s->profiling, mochi::kW1Events);
+  if (rc) return rc;
   // one scratch per signer: a call on another stream waits for the last call's kernels
-  if (s->scratch_used && s->scratch_st != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_scratch, 0));
+  HIP_TRY(s->order.acquire(st));
   HIP_TRY(mochi::launch_w1_decide(a, st));
-  uint64_t* tot = (uint64_t*)s->w1_tot.p;
-  HIP_TRY(hipMemcpyAsync(tot, a.totals, 16, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipEventRecord(s->ev_tot, st));
-  HIP_TRY(hipEventSynchronize(s->ev_tot));
+  if ((rc = x.fetch_totals(a.totals, 16, s->ev_tot, st))) return rc;
+  const uint64_t* tot = (const uint64_t*)x.tot.p;
   o->n_new = (uint32_t)tot[0];
   o->grant_bytes_len = tot[1];
   const bool fits = tot[1] <= o->grant_cap;
@@ -2404,14 +2428,9 @@ int run_write1_issue_device(mochi_signer* s, const mochi_write1_batch* b, mochi_
     }
     if (a.ev) HIP_TRY(hipEventRecord(a.ev[mochi::kW1Events - 1], st));
   }
-  s->w1_ev_valid = a.ev && fits;
-  s->scratch_used = true;
-  s->scratch_st = st;
-  HIP_TRY(hipEventRecord(s->ev_scratch, st));
-  if (!fits)
-    return fail(MOCHI_EINVAL, "grant_cap (%llu) is smaller than the size needed (%llu)", (unsigned long long)o->grant_cap,
-                (unsigned long long)tot[1]);
-  return MOCHI_OK;
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(s->order.release(st));
+  return fits ? MOCHI_OK : capacity_error("grant_cap", o->grant_cap, "size needed", tot[1]);
 }
 
 }  // namespace
@@ -2444,12 +2463,9 @@ int mochi_write1_issue_device(mochi_signer* s, const mochi_write1_batch* b, moch
   o->n_new = 0;
   o->grant_bytes_len = 0;
   std::lock_guard<std::mutex> lk(s->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
-  rc = run_write1_issue_device(s, b, o, (hipStream_t)stream);
-  (void)hipSetDevice(save);
-  return rc;
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  return run_write1_issue_device(s, b, o, (hipStream_t)stream);
 }
 
 int mochi_signer_set_profiling(mochi_signer* s, int on) {
@@ -2462,16 +2478,8 @@ int mochi_signer_set_profiling(mochi_signer* s, int on) {
 int mochi_signer_read_issue_profile(mochi_signer* s, float* kernel_ms, uint32_t n) {
   if (!s || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
-  if (!s->w1_ev_valid) return fail(MOCHI_EINVAL, "no issue call was made while profiling was on");
   static const int kSpan[mochi::kW1Stages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {6, 7}, {7, 8}, {8, 9}};
-  if (hipEventSynchronize(s->w1_ev[mochi::kW1Events - 1]) != hipSuccess)
-    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
-  for (uint32_t i = 0; i < n; i++) {
-    kernel_ms[i] = 0.f;
-    if (i < (uint32_t)mochi::kW1Stages)
-      (void)hipEventElapsedTime(&kernel_ms[i], s->w1_ev[kSpan[i][0]], s->w1_ev[kSpan[i][1]]);
-  }
-  return MOCHI_OK;
+  return s->w1.read_profile(kSpan, mochi::kW1Stages, kernel_ms, n, "no issue call was made while profiling was on");
 }
 
 }  // extern "C"
@@ -2510,19 +2518,14 @@ int run_write1_reply_device(mochi_signer* s, const mochi_write1_batch* b, const 
                             const mochi_write1_reply_source* src, uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off,
                             uint32_t* msg_len, uint8_t* status, uint64_t* wire_len, uint64_t* wire_len_dev,
                             hipStream_t st) {
-  const uint32_t Q = b->n_reqs, O = b->n_ops;
+  const uint32_t Q = b->n_reqs;
+  EncState& x = s->w1r;
   if (wire_len) *wire_len = 0;
-  s->w1r_ev_valid = false;
+  x.ev_valid = false;
   if (Q == 0) {
     if (!wire_len) HIP_TRY(hipMemsetAsync(wire_len_dev, 0, 8, st));
     return MOCHI_OK;
   }
-  int rc;
-  size_t scan_bytes = 0;
-  if (!mochi::w2_small(Q)) HIP_TRY(mochi::w1r_scan_temp_bytes(Q + 1, &scan_bytes));
-  if ((rc = s->w1r_scratch.ensure(mochi::w1r_scratch_bytes(Q, O))) || (rc = s->w1r_scan.ensure(scan_bytes)) ||
-      (rc = s->w1r_tot.ensure(8)))
-    return rc;
   mochi::W1ReplyArgs a;
   memset(&a, 0, sizeof a);
   a.b = *b;
@@ -2533,42 +2536,25 @@ int run_write1_reply_device(mochi_signer* s, const mochi_write1_batch* b, const 
   a.msg_off = msg_off;
   a.msg_len = msg_len;
   a.status = status;
-  a.scan_temp = s->w1r_scan.p;
-  a.scan_temp_bytes = s->w1r_scan.cap;
-  mochi::w1r_carve(a, s->w1r_scratch.p);
-  if (s->profiling) {
-    while (s->w1r_ev.size() < (size_t)mochi::kW1ReplyEvents) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      s->w1r_ev.push_back(e);
-    }
-    a.ev = s->w1r_ev.data();
-  }
+  int rc = x.begin(a, mochi::w1r_layout, mochi::w2_small(Q) ? 0 : Q + 1, 8, s->profiling, mochi::kW1ReplyEvents);
+  if (rc) return rc;
   // one scratch per signer: a call on another stream waits for the last call's kernels
   // (an issue call's included: its outputs are this call's inputs)
-  if (s->scratch_used && s->scratch_st != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_scratch, 0));
+  HIP_TRY(s->order.acquire(st));
   HIP_TRY(mochi::launch_w1r_size(a, st));
   bool fits = true;
   uint64_t need = 0;
   if (wire_len) {
-    uint64_t* tot = (uint64_t*)s->w1r_tot.p;
-    HIP_TRY(hipMemcpyAsync(tot, a.off64 + Q, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s->ev_tot, st));
-    HIP_TRY(hipEventSynchronize(s->ev_tot));
-    *wire_len = need = *tot;
+    if ((rc = x.fetch_totals(a.off64 + Q, 8, s->ev_tot, st))) return rc;
+    *wire_len = need = *(const uint64_t*)x.tot.p;
     fits = need <= wire_cap;
   } else {
     HIP_TRY(hipMemcpyAsync(wire_len_dev, a.off64 + Q, 8, hipMemcpyDeviceToDevice, st));
   }
   if (fits) HIP_TRY(mochi::launch_w1r_emit(a, st));
-  s->w1r_ev_valid = a.ev && fits;
-  s->scratch_used = true;
-  s->scratch_st = st;
-  HIP_TRY(hipEventRecord(s->ev_scratch, st));
-  if (!fits)
-    return fail(MOCHI_EINVAL, "wire_cap (%llu) is smaller than the encoded size (%llu)", (unsigned long long)wire_cap,
-                (unsigned long long)need);
-  return MOCHI_OK;
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(s->order.release(st));
+  return fits ? MOCHI_OK : capacity_error("wire_cap", wire_cap, "encoded size", need);
 }
 
 }  // namespace
@@ -2609,28 +2595,18 @@ int mochi_write1_reply_encode_device(mochi_signer* s, const mochi_write1_batch* 
   int rc = check_write1_reply(b, o, src, wire, wire_cap, msg_off, msg_len, status);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(s->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
-  rc = run_write1_reply_device(s, b, o, src, wire, wire_cap, msg_off, msg_len, status, wire_len, wire_len_dev,
-                               (hipStream_t)stream);
-  (void)hipSetDevice(save);
-  return rc;
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  return run_write1_reply_device(s, b, o, src, wire, wire_cap, msg_off, msg_len, status, wire_len, wire_len_dev,
+                                 (hipStream_t)stream);
 }
 
 int mochi_signer_read_reply_profile(mochi_signer* s, float* kernel_ms, uint32_t n) {
   if (!s || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
-  if (!s->w1r_ev_valid) return fail(MOCHI_EINVAL, "no reply encode call was made while profiling was on");
   static const int kSpan[mochi::kW1ReplyStages][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
-  if (hipEventSynchronize(s->w1r_ev[mochi::kW1ReplyEvents - 1]) != hipSuccess)
-    return fail(MOCHI_EHIP, "hipEventSynchronize failed");
-  for (uint32_t i = 0; i < n; i++) {
-    kernel_ms[i] = 0.f;
-    if (i < (uint32_t)mochi::kW1ReplyStages)
-      (void)hipEventElapsedTime(&kernel_ms[i], s->w1r_ev[kSpan[i][0]], s->w1r_ev[kSpan[i][1]]);
-  }
-  return MOCHI_OK;
+  return s->w1r.read_profile(kSpan, mochi::kW1ReplyStages, kernel_ms, n,
+                             "no reply encode call was made while profiling was on");
 }
 
 }  // extern "C"

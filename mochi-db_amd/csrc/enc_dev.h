@@ -1,8 +1,10 @@
-// enc_dev.h — device byte-output helpers shared by the wire encoders
-// (w2_encode.hip, w1_issue.hip): short header runs gathered into dword stores
-// (Put) and payload copies by aligned 16-byte destination chunks (copy_chunk).
+// enc_dev.h — device helpers shared by the wire encoders (w2_encode.hip,
+// w1_issue.hip, w1_reply.hip): short header runs gathered into dword stores
+// (Put), payload copies by aligned 16-byte destination chunks (copy_chunk,
+// copy_run) and the end of a size kernel (enc_place).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 namespace mochi {
@@ -126,6 +128,40 @@ __device__ __forceinline__ void copy_chunk(uintptr_t d0, const uint8_t* __restri
       *(uint8_t*)(A + i) = (uint8_t)w;
       i++;
     }
+  }
+}
+
+// 16 lanes share two runs (a grant and its signature, a key and its hash) as
+// one list of chunks: lane l takes chunks l, l + 16, ... of the first run and
+// goes on into the second with the chunk index it carried over.  copy_run is
+// one run, from chunk c, and returns the index to start the next run with; an
+// absent next run is the caller's early return before it forms that address.
+__device__ __forceinline__ uint32_t copy_run(uint32_t c, uintptr_t d0, const uint8_t* src, uint32_t len) {
+  const uint32_t n = run_chunks(d0, len);
+#pragma unroll 1
+  for (; c < n; c += 16) copy_chunk(d0, src, len, c);
+  return c - n;
+}
+
+// ---- end of a size kernel ----------------------------------------------------
+// Lane i of n + 1 has the length `mine` of message i (0 for i >= n).  kSmall
+// (one block of 1024 lanes, n < 1024): the 64-bit exclusive scan runs in the
+// block, msg_off[i] and the total off64[n] are final.  Otherwise len64[0, n] is
+// the input of the device-wide scan that follows (enc_launch.h
+// enc_scan_offsets).  EVERY lane of the block must call this, also the lanes
+// past n: the block scan has barriers.
+template <bool kSmall>
+__device__ __forceinline__ void enc_place(uint32_t i, uint32_t n, uint64_t mine, uint64_t* __restrict__ len64,
+                                          uint64_t* __restrict__ off64, uint64_t* __restrict__ msg_off) {
+  if constexpr (kSmall) {
+    using Scan = hipcub::BlockScan<uint64_t, 1024>;
+    __shared__ typename Scan::TempStorage tmp;
+    uint64_t off;
+    Scan(tmp).ExclusiveSum(mine, off);
+    if (i < n) msg_off[i] = off;
+    if (i == n) off64[n] = off;
+  } else {
+    if (i <= n) len64[i] = mine;
   }
 }
 

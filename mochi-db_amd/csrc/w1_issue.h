@@ -59,11 +59,10 @@ struct W1Args {
 };
 constexpr int kW1Events = 10;  // the last one is recorded by the caller after signing
 constexpr int kW1Stages = 8;
-// bytes of one call's scratch (every array 16-byte aligned)
-size_t w1_scratch_bytes(uint32_t Q, uint32_t O);
-// carve `base` (w1_scratch_bytes long) into a's scratch arrays; a.b and a.slots set
-void w1_carve(W1Args& a, void* base);
-hipError_t w1_scan_temp_bytes(uint32_t n, size_t* bytes);
+// The per-call scratch layout (a.b and a.slots set; every array 16-byte aligned): on a
+// null base it only counts and returns the bytes to allocate; on that allocation it
+// sets a's scratch pointers.
+size_t w1_layout(W1Args& a, void* base);
 // decisions, kinds, reply sizes and the scans: fills op_decision / req_kind /
 // req_grant_off and totals[2]
 hipError_t launch_w1_decide(const W1Args& a, hipStream_t stream);

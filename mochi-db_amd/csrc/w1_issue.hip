@@ -22,6 +22,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "enc_dev.h"
+#include "enc_launch.h"
 #include "prep_dev.h"
 #include "w1_issue.h"
 #include "w2.h"
@@ -309,59 +310,37 @@ __global__ __launch_bounds__(256) void k_w1_emit(mochi_write1_batch b, mochi_wri
     out.grant_op[g] = o;
     out.grant_ts[g] = ts;
   }
-  const uint32_t n1 = run_chunks(d_key, kl);
-  const uint8_t* key = b.strings + b.op_key_off[o];
-  uint32_t c = l;
-#pragma unroll 1
-  for (; c < n1; c += 16) copy_chunk(d_key, key, kl, c);
+  const uint32_t c = copy_run(l, d_key, b.strings + b.op_key_off[o], kl);
   if (!hl) return;
-  const uint32_t n2 = run_chunks(d_hash, hl);
-  const uint8_t* hash = b.strings + b.req_hash_off[q];
-#pragma unroll 1
-  for (c -= n1; c < n2; c += 16) copy_chunk(d_hash, hash, hl, c);
+  copy_run(c, d_hash, b.strings + b.req_hash_off[q], hl);
 }
 
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline bool w1_small(uint32_t Q, uint32_t O) { return w2_small(O) && w2_small(Q); }
 
 }  // namespace
 
-size_t w1_scratch_bytes(uint32_t Q, uint32_t O) {
-  const size_t o1 = (size_t)O + 1, q1 = (size_t)Q + 1, slots = (size_t)w1_table_slots(O);
-  return up16(8 * slots) + up16(4 * slots) + 2 * up16(4 * o1) + up16(o1) + 4 * up16(8 * o1) + 2 * up16(8 * q1) + 16 + 16;
-}
-
-void w1_carve(W1Args& a, void* base) {
+size_t w1_layout(W1Args& a, void* base) {
   const size_t o1 = (size_t)a.b.n_ops + 1, q1 = (size_t)a.b.n_reqs + 1;
-  uint8_t* p = (uint8_t*)(((uintptr_t)base + 15) & ~(uintptr_t)15);
-  auto take = [&](size_t bytes) {
-    uint8_t* r = p;
-    p += up16(bytes);
-    return r;
-  };
-  a.tbl_key = (uint64_t*)take(8 * (size_t)a.slots);  // tbl_key and tbl_val adjacent: one fill (launch_w1_decide)
-  a.tbl_val = (uint32_t*)take(4 * (size_t)a.slots);
-  a.op_req = (uint32_t*)take(4 * o1);
-  a.op_ref = (uint32_t*)take(4 * o1);
-  a.op_dead = (uint8_t*)take(o1);
-  a.cnt64 = (uint64_t*)take(8 * o1);
-  a.len64 = (uint64_t*)take(8 * o1);
-  a.cnt_off = (uint64_t*)take(8 * o1);
-  a.len_off = (uint64_t*)take(8 * o1);
-  a.ref64 = (uint64_t*)take(8 * q1);
-  a.ref_off = (uint64_t*)take(8 * q1);
-  a.totals = (uint64_t*)take(16);
-}
-
-hipError_t w1_scan_temp_bytes(uint32_t n, size_t* bytes) {
-  return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n);
+  Carve c(base);
+  a.tbl_key = c.take<uint64_t>(a.slots);  // tbl_key and tbl_val adjacent: one fill (launch_w1_decide)
+  a.tbl_val = c.take<uint32_t>(a.slots);
+  a.op_req = c.take<uint32_t>(o1);
+  a.op_ref = c.take<uint32_t>(o1);
+  a.op_dead = c.take<uint8_t>(o1);
+  a.cnt64 = c.take<uint64_t>(o1);
+  a.len64 = c.take<uint64_t>(o1);
+  a.cnt_off = c.take<uint64_t>(o1);
+  a.len_off = c.take<uint64_t>(o1);
+  a.ref64 = c.take<uint64_t>(q1);
+  a.ref_off = c.take<uint64_t>(q1);
+  a.totals = c.take<uint64_t>(2);
+  return c.bytes();
 }
 
 hipError_t launch_w1_decide(const W1Args& a, hipStream_t st) {
   const mochi_write1_batch& b = a.b;
   const uint32_t O = b.n_ops, Q = b.n_reqs, mask = a.slots - 1;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(0);
   if (e != hipSuccess) return e;
   // every key word empty, every value word "no op"
@@ -383,12 +362,10 @@ hipError_t launch_w1_decide(const W1Args& a, hipStream_t st) {
     hipLaunchKernelGGL(k_w1_scan_small, dim3(1), dim3(1024), 0, st, O, Q, a.cnt64, a.len64, a.ref64, a.cnt_off, a.len_off,
                        a.ref_off);
   } else {
-    size_t tb = a.scan_temp_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.cnt64, a.cnt_off, (int)(O + 1), st)) != hipSuccess) return e;
-    tb = a.scan_temp_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.len64, a.len_off, (int)(O + 1), st)) != hipSuccess) return e;
-    tb = a.scan_temp_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.ref64, a.ref_off, (int)(Q + 1), st)) != hipSuccess) return e;
+    if ((e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.cnt64, a.cnt_off, O + 1, st)) != hipSuccess ||
+        (e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.len64, a.len_off, O + 1, st)) != hipSuccess ||
+        (e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.ref64, a.ref_off, Q + 1, st)) != hipSuccess)
+      return e;
   }
   hipLaunchKernelGGL(k_w1_totals, dim3(cdiv((uint64_t)Q + 1, 256)), dim3(256), 0, st, O, Q, a.cnt_off, a.len_off, a.ref_off,
                      a.o.req_grant_off, a.totals);
@@ -399,7 +376,7 @@ hipError_t launch_w1_decide(const W1Args& a, hipStream_t st) {
 hipError_t launch_w1_emit(const W1Args& a, hipStream_t st) {
   const mochi_write1_batch& b = a.b;
   const uint32_t O = b.n_ops, Q = b.n_reqs;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(6);
   if (e != hipSuccess) return e;
   if (O)

@@ -9,26 +9,9 @@
 #include <vector>
 
 #include "w1_issue.h"
+#include "wire_put.h"
 
 namespace mochi_host {
-namespace {
-
-uint8_t* put_varint(uint8_t* o, uint64_t v) {
-  while (v >= 0x80) {
-    *o++ = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  *o++ = (uint8_t)v;
-  return o;
-}
-uint8_t* put_ld(uint8_t* o, uint8_t tag, const uint8_t* p, uint64_t n) {
-  *o++ = tag;
-  o = put_varint(o, n);
-  if (n) memcpy(o, p, n);
-  return o + n;
-}
-
-}  // namespace
 
 int write1_issue(const mochi_write1_batch* b, mochi_write1_issued* out, const char** err) {
   using namespace mochi;
@@ -44,7 +27,7 @@ int write1_issue(const mochi_write1_batch* b, mochi_write1_issued* out, const ch
     if (b->req_op_off[q + 1] - b->req_op_off[q] > MOCHI_MAX_OPS_PER_CERT)
       return bad("a request has more than MOCHI_MAX_OPS_PER_CERT ops");
   }
-  auto in_strings = [&](uint64_t off, uint32_t len) { return off <= b->strings_len && len <= b->strings_len - off; };
+  auto in_strings = [&](uint64_t off, uint32_t len) { return inside(off, len, b->strings_len); };
   for (uint32_t q = 0; q < Q; q++)
     if (!in_strings(b->req_hash_off[q], b->req_hash_len[q])) return bad("a transactionHash lies outside strings");
   for (uint32_t s = 0; s < S; s++)

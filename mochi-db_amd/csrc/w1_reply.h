@@ -76,11 +76,10 @@ struct W1ReplyArgs {
 };
 constexpr int kW1ReplyEvents = 6;
 constexpr int kW1ReplyStages = 4;  // k_w1r_size, scan, k_w1r_hdr, k_w1r_copy
-// bytes of one call's scratch (every array 16-byte aligned)
-size_t w1r_scratch_bytes(uint32_t Q, uint32_t O);
-// carve `base` (w1r_scratch_bytes long) into a's scratch arrays; a.b set
-void w1r_carve(W1ReplyArgs& a, void* base);
-hipError_t w1r_scan_temp_bytes(uint32_t n, size_t* bytes);
+// The per-call scratch layout (a.b set; every array 16-byte aligned): on a null base it
+// only counts and returns the bytes to allocate; on that allocation it sets a's
+// scratch pointers.
+size_t w1r_layout(W1ReplyArgs& a, void* base);
 // sizes + the 64-bit exclusive scan: fills msg_off / msg_len / status and off64[Q]
 hipError_t launch_w1r_size(const W1ReplyArgs& a, hipStream_t stream);
 // headers + payload copy; every kernel writes nothing when off64[Q] > wire_cap

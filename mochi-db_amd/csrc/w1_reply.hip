@@ -22,6 +22,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "enc_dev.h"
+#include "enc_launch.h"
 #include "w1_reply.h"
 #include "w2.h"
 
@@ -97,16 +98,7 @@ __global__ __launch_bounds__(kSmall ? 1024 : 256) void k_w1r_size(mochi_write1_b
     msg_len[q] = (uint32_t)mine;
     req_mg[q] = (uint32_t)mg;
   }
-  if constexpr (kSmall) {
-    using Scan = hipcub::BlockScan<uint64_t, 1024>;
-    __shared__ typename Scan::TempStorage tmp;
-    uint64_t off;
-    Scan(tmp).ExclusiveSum(mine, off);
-    if (q < Q) msg_off[q] = off;
-    if (q == Q) off64[Q] = off;
-  } else {
-    if (q <= Q) len64[q] = mine;
-  }
+  enc_place<kSmall>(q, Q, mine, len64, off64, msg_off);
 }
 
 // ---- headers: lane = request ----------------------------------------------------
@@ -203,18 +195,10 @@ __global__ __launch_bounds__(256) void k_w1r_copy(mochi_write1_batch b, mochi_wr
     const uint64_t dg = ent_dst[3 * e], ds = ent_dst[3 * e + 1];
     const uint8_t *src = nullptr, *sig = nullptr;
     const uint32_t gl = ref_grant(o, s, b.n_stored, o.req_grant[e], &src, &sig);
-    uint32_t c = l, n1 = 0;
-    if (dg != kNone && gl) {
-      const uintptr_t d0 = (uintptr_t)(wire + dg);
-      n1 = run_chunks(d0, gl);
-#pragma unroll 1
-      for (; c < n1; c += 16) copy_chunk(d0, src, gl, c);
-    }
+    uint32_t c = l;
+    if (dg != kNone && gl) c = copy_run(c, (uintptr_t)(wire + dg), src, gl);
     if (ds == kNone || !sig) return;
-    const uintptr_t d1 = (uintptr_t)(wire + ds);
-    const uint32_t n2 = run_chunks(d1, MOCHI_RSA_BYTES);
-#pragma unroll 1
-    for (c -= n1; c < n2; c += 16) copy_chunk(d1, sig, MOCHI_RSA_BYTES, c);
+    copy_run(c, (uintptr_t)(wire + ds), sig, MOCHI_RSA_BYTES);
     return;
   }
   const uint64_t e = ((uint64_t)(blockIdx.x - small_blocks) * blockDim.x + threadIdx.x) >> 6;
@@ -230,38 +214,22 @@ __global__ __launch_bounds__(256) void k_w1r_copy(mochi_write1_batch b, mochi_wr
   for (uint32_t c = threadIdx.x & 63; c < n; c += 64) copy_chunk(d0, cert, cl, c);
 }
 
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
-size_t w1r_scratch_bytes(uint32_t Q, uint32_t O) {
-  const size_t q1 = (size_t)Q + 1, n = O;
-  return up16(4 * n) + up16(24 * n) + up16(4 * q1) + 2 * up16(8 * q1) + 16;
-}
-
-void w1r_carve(W1ReplyArgs& a, void* base) {
+size_t w1r_layout(W1ReplyArgs& a, void* base) {
   const size_t q1 = (size_t)a.b.n_reqs + 1, n = a.b.n_ops;
-  uint8_t* p = (uint8_t*)(((uintptr_t)base + 15) & ~(uintptr_t)15);
-  auto take = [&](size_t bytes) {
-    uint8_t* r = p;
-    p += up16(bytes);
-    return r;
-  };
-  a.ent_op = (uint32_t*)take(4 * n);
-  a.ent_dst = (uint64_t*)take(24 * n);
-  a.req_mg = (uint32_t*)take(4 * q1);
-  a.len64 = (uint64_t*)take(8 * q1);
-  a.off64 = (uint64_t*)take(8 * q1);
-}
-
-hipError_t w1r_scan_temp_bytes(uint32_t n, size_t* bytes) {
-  return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n);
+  Carve c(base);
+  a.ent_op = c.take<uint32_t>(n);
+  a.ent_dst = c.take<uint64_t>(3 * n);
+  a.req_mg = c.take<uint32_t>(q1);
+  a.len64 = c.take<uint64_t>(q1);
+  a.off64 = c.take<uint64_t>(q1);
+  return c.bytes();
 }
 
 hipError_t launch_w1r_size(const W1ReplyArgs& a, hipStream_t st) {
   const uint32_t Q = a.b.n_reqs;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(0);
   if (e != hipSuccess) return e;
   if (w2_small(Q)) {
@@ -274,17 +242,14 @@ hipError_t launch_w1r_size(const W1ReplyArgs& a, hipStream_t st) {
                      a.req_mg, a.msg_len, a.status, a.len64, a.off64, a.msg_off);
   e = hipGetLastError();
   if (e != hipSuccess || (e = stamp(1)) != hipSuccess) return e;
-  size_t tb = a.scan_temp_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.len64, a.off64, (int)(Q + 1), st);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(a.msg_off, a.off64, 8 * (size_t)Q, hipMemcpyDeviceToDevice, st);
+  e = enc_scan_offsets(a.scan_temp, a.scan_temp_bytes, a.len64, a.off64, a.msg_off, Q, st);
   return e != hipSuccess ? e : stamp(2);
 }
 
 hipError_t launch_w1r_emit(const W1ReplyArgs& a, hipStream_t st) {
   const uint32_t Q = a.b.n_reqs, O = a.b.n_ops;
   const uint64_t* total = a.off64 + Q;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(3);
   if (e != hipSuccess) return e;
   if (Q)

@@ -7,24 +7,10 @@
 #include <vector>
 
 #include "w1_reply.h"
+#include "wire_put.h"
 
 namespace mochi_host {
 namespace {
-
-uint8_t* put_varint(uint8_t* o, uint64_t v) {
-  while (v >= 0x80) {
-    *o++ = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  *o++ = (uint8_t)v;
-  return o;
-}
-uint8_t* put_ld(uint8_t* o, uint8_t tag, const uint8_t* p, uint64_t n) {
-  *o++ = tag;
-  o = put_varint(o, n);
-  if (n) memcpy(o, p, n);
-  return o + n;
-}
 
 // one listed grant of a reply
 struct Entry {
@@ -44,7 +30,6 @@ int write1_reply_encode(const mochi_write1_batch* b, const mochi_write1_issued* 
     *err = what;
     return MOCHI_EINVAL;
   };
-  auto inside = [](uint64_t off, uint32_t len, uint64_t blob) { return off <= blob && len <= blob - off; };
   *wire_len = 0;
   if (b->req_op_off[0] != 0 || b->req_op_off[Q] != O) return bad("req_op_off is not a CSR over n_ops");
   if (o->req_grant_off[0] != 0 || o->req_grant_off[Q] > O) return bad("req_grant_off is not a CSR of at most n_ops references");

@@ -76,11 +76,13 @@ struct W2EncArgs {
 };
 constexpr int kW2EncEvents = 8;
 constexpr int kW2EncStages = 6;  // k_enc_mg, k_enc_msg, scan, k_enc_hdr_mg, k_enc_hdr_msg, k_enc_copy
-// bytes of one encode's per-batch scratch (every array 16-byte aligned)
-size_t w2_enc_scratch_bytes(uint32_t M, uint32_t n_mgs, uint32_t N);
-// carve `base` (16-byte aligned, w2_enc_scratch_bytes long) into a's scratch arrays
-void w2_enc_carve(W2EncArgs& a, void* base);
-hipError_t w2_enc_scan_temp_bytes(uint32_t n, size_t* bytes);
+// The per-batch scratch layout (a.src set; every array 16-byte aligned): on a null base
+// it only counts and returns the bytes to allocate; on that allocation it sets a's
+// scratch pointers.
+size_t w2_enc_layout(W2EncArgs& a, void* base);
+// temp bytes of a 64-bit device scan over n elements; one function for the three
+// encoders (w2_encode.hip, w1_issue.hip, w1_reply.hip), see enc_launch.h
+hipError_t enc_scan_temp_bytes(uint32_t n, size_t* bytes);
 // sizes + the 64-bit exclusive scan: fills msg_off / msg_len / status and off64[M]
 hipError_t launch_w2_enc_size(const W2EncArgs& a, hipStream_t stream);
 // headers + payload copy (after the caller has checked off64[M] against the capacity)

@@ -20,6 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "enc_dev.h"
+#include "enc_launch.h"
 #include "proto_dev.h"
 #include "w2.h"
 #include "w2_encode.h"
@@ -114,16 +115,7 @@ __global__ __launch_bounds__(kSmall ? 1024 : 256) void k_enc_msg(mochi_write2_so
     msg_wc[m] = (uint32_t)wc;
     msg_tx[m] = (uint32_t)tx;
   }
-  if constexpr (kSmall) {
-    using Scan = hipcub::BlockScan<uint64_t, 1024>;
-    __shared__ typename Scan::TempStorage tmp;
-    uint64_t off;
-    Scan(tmp).ExclusiveSum(mine, off);
-    if (m < M) msg_off[m] = off;
-    if (m == M) off64[M] = off;
-  } else {
-    if (m <= M) len64[m] = mine;
-  }
+  enc_place<kSmall>(m, M, mine, len64, off64, msg_off);
 }
 
 // ---- headers: lane = MultiGrant --------------------------------------------
@@ -230,60 +222,38 @@ __global__ __launch_bounds__(256) void k_enc_copy(mochi_write2_source s, const u
   if (g >= s.n_grants) return;
   const uint64_t dg = g_dst[2 * g], ds = g_dst[2 * g + 1];
   if (dg == kNone) return;  // a grant of no emitted message
-  const uint32_t gl = s.grant_len[g];
-  const uintptr_t d0 = (uintptr_t)(wire + dg);
-  const uint8_t* src = s.grant_bytes + s.grant_off[g];
-  const uint32_t n1 = run_chunks(d0, gl);
-  uint32_t c = q;
-#pragma unroll 1
-  for (; c < n1; c += 16) copy_chunk(d0, src, gl, c);
+  const uint32_t c = copy_run(q, (uintptr_t)(wire + dg), s.grant_bytes + s.grant_off[g], s.grant_len[g]);
   if (ds == kNone) return;
-  const uintptr_t d1 = (uintptr_t)(wire + ds);
-  const uint32_t n2 = run_chunks(d1, MOCHI_RSA_BYTES);
-  const uint8_t* sg = s.sig + (size_t)MOCHI_RSA_BYTES * g;
-#pragma unroll 1
-  for (c -= n1; c < n2; c += 16) copy_chunk(d1, sg, MOCHI_RSA_BYTES, c);
+  copy_run(c, (uintptr_t)(wire + ds), s.sig + (size_t)MOCHI_RSA_BYTES * g, MOCHI_RSA_BYTES);
 }
-
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
 
-size_t w2_enc_scratch_bytes(uint32_t M, uint32_t n_mgs, uint32_t N) {
-  const size_t m1 = (size_t)M + 1, nm = n_mgs, n = N;
-  return up16(16 * n) + up16(4 * nm) + up16(8 * n) + up16(8 * nm) + up16(4 * nm) + up16(nm) + 2 * up16(4 * m1) +
-         2 * up16(8 * m1) + 16;
-}
-
-void w2_enc_carve(W2EncArgs& a, void* base) {
+size_t w2_enc_layout(W2EncArgs& a, void* base) {
   const size_t m1 = (size_t)a.src.n_msgs + 1, nm = a.src.n_mgs, n = a.src.n_grants;
-  uint8_t* p = (uint8_t*)(((uintptr_t)base + 15) & ~(uintptr_t)15);
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p;
-    p += up16(bytes);
-    return q;
-  };
-  a.g_dst = (uint64_t*)take(16 * n);  // g_dst and mg_msg adjacent: one fill (launch_w2_enc_size)
-  a.mg_msg = (uint32_t*)take(4 * nm);
-  a.g_oid = (uint32_t*)take(8 * n);
-  a.mg_gpart = (uint64_t*)take(8 * nm);
-  a.mg_rel = (uint32_t*)take(4 * nm);
-  a.mg_bad = (uint8_t*)take(nm);
-  a.msg_wc = (uint32_t*)take(4 * m1);
-  a.msg_tx = (uint32_t*)take(4 * m1);
-  a.len64 = (uint64_t*)take(8 * m1);
-  a.off64 = (uint64_t*)take(8 * m1);
+  Carve c(base);
+  a.g_dst = c.take<uint64_t>(2 * n);  // g_dst and mg_msg adjacent: one fill (launch_w2_enc_size)
+  a.mg_msg = c.take<uint32_t>(nm);
+  a.g_oid = c.take<uint32_t>(2 * n);
+  a.mg_gpart = c.take<uint64_t>(nm);
+  a.mg_rel = c.take<uint32_t>(nm);
+  a.mg_bad = c.take<uint8_t>(nm);
+  a.msg_wc = c.take<uint32_t>(m1);
+  a.msg_tx = c.take<uint32_t>(m1);
+  a.len64 = c.take<uint64_t>(m1);
+  a.off64 = c.take<uint64_t>(m1);
+  return c.bytes();
 }
 
-hipError_t w2_enc_scan_temp_bytes(uint32_t n, size_t* bytes) {
+// declared in w2_encode.h for capi.cpp, which cannot include hipcub
+hipError_t enc_scan_temp_bytes(uint32_t n, size_t* bytes) {
   return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n);
 }
 
 hipError_t launch_w2_enc_size(const W2EncArgs& a, hipStream_t st) {
   const mochi_write2_source& s = a.src;
   const uint32_t M = s.n_msgs;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(0);
   if (e != hipSuccess) return e;
   // "no destination" / "no message" until the header kernels say otherwise
@@ -302,16 +272,13 @@ hipError_t launch_w2_enc_size(const W2EncArgs& a, hipStream_t st) {
                      a.off64, a.msg_off);
   e = hipGetLastError();
   if (e != hipSuccess || (e = stamp(2)) != hipSuccess) return e;
-  size_t tb = a.scan_temp_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(a.scan_temp, tb, a.len64, a.off64, (int)(M + 1), st);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(a.msg_off, a.off64, 8 * (size_t)M, hipMemcpyDeviceToDevice, st);
+  e = enc_scan_offsets(a.scan_temp, a.scan_temp_bytes, a.len64, a.off64, a.msg_off, M, st);
   return e != hipSuccess ? e : stamp(3);
 }
 
 hipError_t launch_w2_enc_emit(const W2EncArgs& a, hipStream_t st) {
   const mochi_write2_source& s = a.src;
-  auto stamp = [&](int i) { return a.ev ? hipEventRecord(a.ev[i], st) : hipSuccess; };
+  const Stamps stamp{a.ev, st};
   hipError_t e = stamp(4);
   if (e != hipSuccess) return e;
   if (s.n_mgs)

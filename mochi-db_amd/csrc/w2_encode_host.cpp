@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "w2_encode.h"
+#include "wire_put.h"
 
 namespace mochi_host {
 namespace {
@@ -79,21 +80,6 @@ bool rd_string(Rd& r, uint32_t& off, uint32_t& len) {
   len = (uint32_t)l32;
   r.pos += (uint32_t)l32;
   return true;
-}
-
-uint8_t* put_varint(uint8_t* o, uint64_t v) {
-  while (v >= 0x80) {
-    *o++ = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  *o++ = (uint8_t)v;
-  return o;
-}
-uint8_t* put_ld(uint8_t* o, uint8_t tag, const uint8_t* p, uint64_t n) {
-  *o++ = tag;
-  o = put_varint(o, n);
-  if (n) memcpy(o, p, n);
-  return o + n;
 }
 
 }  // namespace
@@ -184,7 +170,7 @@ int write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32
   if (!csr(s->cert_mg_off, M, NM)) return bad("cert_mg_off is not a CSR over n_mgs");
   if (!csr(s->mg_grant_off, NM, N)) return bad("mg_grant_off is not a CSR over n_grants");
   if (!csr(s->cert_op_off, M, O)) return bad("cert_op_off is not a CSR over n_ops");
-  auto in_strings = [&](uint64_t off, uint32_t len) { return off <= s->strings_len && len <= s->strings_len - off; };
+  auto in_strings = [&](uint64_t off, uint32_t len) { return inside(off, len, s->strings_len); };
   for (uint32_t o = 0; o < O; o++)
     if (!in_strings(s->op1_off[o], s->op1_len[o]) || (s->op2_off && !in_strings(s->op2_off[o], s->op2_len[o])))
       return bad("an operand lies outside strings");
@@ -202,7 +188,7 @@ int write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32
       const uint64_t go = s->grant_off[g];
       const uint32_t gl = s->grant_len[g];
       uint32_t oo = 0, ol = 0;
-      if (go > s->grant_bytes_len || gl > s->grant_bytes_len - go || !grant_object_id(s->grant_bytes + go, gl, oo, ol)) {
+      if (!inside(go, gl, s->grant_bytes_len) || !grant_object_id(s->grant_bytes + go, gl, oo, ol)) {
         mg_bad[i] = 1;
         continue;
       }

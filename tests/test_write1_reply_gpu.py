@@ -173,8 +173,9 @@ def test_device_side_capacity_rule(signer, own_cases, name):
 
 
 # 5. issue -> sign -> reply bytes as one enqueue ------------------------------------------------
-def _issue_and_reply(signer, batch, src, stream):
-    """issue_device(sign) then the reply encoder in mode 2 on `stream`, nothing in between."""
+def _issue_and_reply(signer, batch, src, stream, reply_stream=None):
+    """issue_device(sign) on `stream`, then the reply encoder in mode 2 on `reply_stream` (default: the same), nothing
+    in between."""
     import torch
 
     db, ds = mh.DeviceWrite1Batch(batch, 0), mh.DeviceWrite1ReplySource(src, 0)
@@ -182,8 +183,11 @@ def _issue_and_reply(signer, batch, src, stream):
     cap = mh.write1_reply_bound(batch, src, out.grant_cap, True)  # sized before anything is known
     outs = _outputs(batch.n_reqs, cap)
     total = torch.full((1,), -1, dtype=torch.int64, device="cuda:0")
+    if reply_stream is not None:
+        torch.cuda.synchronize()  # the uploads and fills above went to the current stream
     assert signer.issue_device(db, out, stream=stream) == mh.OK
-    rc, _ = signer.reply_encode_device(db, out, ds, *outs, stream=stream, wire_len_dev=total)
+    rc, _ = signer.reply_encode_device(db, out, ds, *outs, wire_len_dev=total,
+                                       stream=stream if reply_stream is None else reply_stream)
     assert rc == mh.OK
     return out, outs, total
 
@@ -197,16 +201,21 @@ def _bodies(outs, total, Q):
     return [w[int(off[q]):int(off[q]) + int(ln[q])].tobytes() for q in range(Q)]
 
 
+def _chained_case(pems):
+    batch = W.make_write1_batch(300, 2, contention=0.3)
+    stored = [b"\x0a\x03old\x10%c" % (i % 100 + 1) for i in range(batch.n_stored)]  # grants given before the batch
+    src = RM.make_source(batch, stored, certs=True, sigs=False)
+    src.stored_sig = mh.sign_grants(pems[0], *RM.pack(stored))
+    return batch, src
+
+
 def test_chained_issue_sign_reply_without_synchronisation(pems, signer):
     pytest.importorskip("google.protobuf")
     import torch
 
     Reply, Grant = RM.classes()
-    batch = W.make_write1_batch(300, 2, contention=0.3)
+    batch, src = _chained_case(pems)
     host = mh.write1_issue(batch)
-    stored = [b"\x0a\x03old\x10%c" % (i % 100 + 1) for i in range(batch.n_stored)]  # grants given before the batch
-    src = RM.make_source(batch, stored, certs=True, sigs=False)
-    src.stored_sig = mh.sign_grants(pems[0], *RM.pack(stored))
     out, outs, total = _issue_and_reply(signer, batch, src, _stream())
     torch.cuda.synchronize()  # the only one
     got = out.to_host()
@@ -226,6 +235,21 @@ def test_chained_issue_sign_reply_without_synchronisation(pems, signer):
     cpu = mh.sign_grants(pems[0], *RM.pack([gb for gb, _ in pairs]))  # one call: the CPU signer over every grant
     for i, (gb, sig) in enumerate(pairs):
         assert sig == cpu[i].tobytes(), i
+
+
+def test_issue_and_reply_on_different_streams(pems, signer):
+    """The reply call reads what the issue call's kernels are still writing: only the signer's scratch order (one for
+    both calls) makes stream B wait for stream A."""
+    import torch
+
+    batch, src = _chained_case(pems)
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    out, outs, total = _issue_and_reply(signer, batch, src, a.cuda_stream, b.cuda_stream)
+    torch.cuda.synchronize()  # the only one after the two calls
+    got = out.to_host()
+    want, _, _, _ = mh.write1_reply_encode(batch, got, src)
+    assert b"".join(_bodies(outs, total, batch.n_reqs)) == want.tobytes()
+    assert signer.rejected() == 0
 
 
 # 6. four servers' replies become Write2ToServer bodies the verifier accepts -----------------------
