@@ -4,7 +4,6 @@
 // The verify path it drives replaces, in the reference,
 //   InMemoryDataStore.processWrite2ToServer  (InMemoryDataStore.java:641-666)
 // with one batched call over many certificates.
-#include <hip/hip_runtime.h>
 #include <openssl/bn.h>
 #include <openssl/core_names.h>
 #include <openssl/evp.h>
@@ -13,26 +12,17 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <string>
-#include <vector>
 
-#include "../../include/mochi_hip.h"
-#include "kernels.h"
+#include "ctx.h"
 #include "mont.h"
 #include "w1_issue.h"
 #include "w1_reply.h"
-#include "w2.h"
-#include "w2_encode.h"
-#include "w2_host.h"
 
-namespace {
+using namespace mochi;
 
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
+int mochi::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -41,6 +31,8 @@ int fail(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
+
+namespace {
 
 bool prep_serial() {
   static const bool v = [] {
@@ -58,165 +50,16 @@ bool fixup_kernel() {
   return v;
 }
 
-bool copy_streams() {
-  static const bool v = [] {
-    const char* e = getenv("MOCHI_COPY_STREAMS");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
-
 uint32_t default_chunk_grants() {
   const char* e = getenv("MOCHI_CHUNK_GRANTS");
   const long x = e ? atol(e) : 0;
   return (uint32_t)(x > 0 ? x : 262144);
 }
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return fail(MOCHI_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
-// Growable device allocation.
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return MOCHI_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes < 256 ? 256 : bytes;
-    if (hipMalloc(&p, want) != hipSuccess) return fail(MOCHI_ENOMEM, "hipMalloc(%zu) failed", want);
-    cap = want;
-    return MOCHI_OK;
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return MOCHI_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess)
-      return fail(MOCHI_ENOMEM, "hipHostMalloc(%zu) failed", want);
-    cap = want;
-    return MOCHI_OK;
-  }
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
-// What one wire encoder (w2_encode.hip, w1_issue.hip, w1_reply.hip) keeps between calls.
-struct EncState {
-  DevBuf scratch, scan;        // per-call scratch; temp of the device-wide scan
-  PinnedBuf tot;               // the totals the host waits for
-  std::vector<hipEvent_t> ev;  // per-kernel events of the last call made while profiling, created on first use
-  bool ev_valid = false;       // ev holds a whole call: read_profile may read it
-  // scan_n: elements of the device-wide 64-bit scan, 0 on the single-block path (no temp)
-  int prepare(size_t scratch_bytes, uint32_t scan_n, size_t tot_bytes) {
-    size_t scan_bytes = 0;
-    if (scan_n) HIP_TRY(mochi::enc_scan_temp_bytes(scan_n, &scan_bytes));
-    int rc;
-    if ((rc = scratch.ensure(scratch_bytes)) || (rc = scan.ensure(scan_bytes))) return rc;
-    return tot.ensure(tot_bytes);
-  }
-  // *out = n events to stamp while profiling, null otherwise
-  int events(bool profiling, int n, hipEvent_t** out) {
-    ev_valid = false;
-    *out = nullptr;
-    while (profiling && ev.size() < (size_t)n) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      ev.push_back(e);
-    }
-    if (profiling) *out = ev.data();
-    return MOCHI_OK;
-  }
-  // all a call needs before its first launch: the buffers, a's scratch pointers through the
-  // encoder's one layout function, its scan temp and its events
-  template <class Args>
-  int begin(Args& a, size_t (*layout)(Args&, void*), uint32_t scan_n, size_t tot_bytes, bool profiling, int n_ev) {
-    int rc;
-    if ((rc = prepare(layout(a, nullptr), scan_n, tot_bytes)) || (rc = events(profiling, n_ev, &a.ev))) return rc;
-    a.scan_temp = scan.p;
-    a.scan_temp_bytes = scan.cap;
-    layout(a, scratch.p);
-    return MOCHI_OK;
-  }
-  // the totals the size phase left at `dev`, in tot.p once this returns
-  int fetch_totals(const void* dev, size_t bytes, hipEvent_t ev_tot, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(tot.p, dev, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ev_tot, st));
-    HIP_TRY(hipEventSynchronize(ev_tot));
-    return MOCHI_OK;
-  }
-  // kernel_ms[i] = time between events span[i][0] and span[i][1] of the last profiled call
-  int read_profile(const int (*span)[2], int n_stages, float* kernel_ms, uint32_t n, const char* none_msg) {
-    if (!ev_valid) return fail(MOCHI_EINVAL, "%s", none_msg);
-    if (hipEventSynchronize(ev.back()) != hipSuccess) return fail(MOCHI_EHIP, "hipEventSynchronize failed");
-    for (uint32_t i = 0; i < n; i++) {
-      kernel_ms[i] = 0.f;
-      if (i < (uint32_t)n_stages) (void)hipEventElapsedTime(&kernel_ms[i], ev[span[i][0]], ev[span[i][1]]);
-    }
-    return MOCHI_OK;
-  }
-  ~EncState() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-  }
-};
-
-// Scratch ordering across calls and streams: every launch that uses its owner's scratch
-// waits for the previous one to be done with it (the device entry points are async on a
-// caller-chosen stream, so two calls on different streams would otherwise race on it).
-struct ScratchOrder {
-  hipEvent_t ev = nullptr;  // created and destroyed by the owner
-  bool used = false;
-  hipStream_t st = nullptr;  // the stream ev was last recorded on
-  hipError_t acquire(hipStream_t s) {
-    // on the stream that last released the scratch, stream order already holds
-    // (a wait there is one more API call and barrier packet per small batch)
-    return used && st != s ? hipStreamWaitEvent(s, ev, 0) : hipSuccess;
-  }
-  hipError_t release(hipStream_t s) {
-    used = true;
-    st = s;
-    return hipEventRecord(ev, s);
-  }
-};
-
-// the device of a context or signer for one call; the caller's device again on return
-struct DeviceGuard {
-  int save = 0;
-  bool ok;
-  explicit DeviceGuard(int device) {
-    (void)hipGetDevice(&save);
-    ok = hipSetDevice(device) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (ok) (void)hipSetDevice(save);
-  }
-};
-
 int capacity_error(const char* cap_name, uint64_t cap, const char* need_name, uint64_t need) {
   return fail(MOCHI_EINVAL, "%s (%llu) is smaller than the %s (%llu)", cap_name, (unsigned long long)cap, need_name,
               (unsigned long long)need);
 }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- host-side key precompute (OpenSSL BN, setup only) --------------------
 
@@ -364,63 +207,6 @@ int set_error(int code, const std::string& msg) {
 }
 }  // namespace mochi
 
-struct mochi_ctx {
-  // batchers built on this context (mochi_batcher_create*) hold it until they
-  // are freed -- a batcher destroyed from its own callback is freed later by
-  // its last flusher thread, which still uses the context's streams and pinned
-  // buffers until then.  mochi_ctx_destroy with a holder left never blocks: it
-  // marks the context and the last holder's release frees it.
-  std::mutex ref_mu;
-  int batcher_refs = 0;
-  bool destroy_pending = false;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  uint32_t n_keys = 0;
-  mochi::KeyEntry* d_keys = nullptr;
-  mochi::FoldKey* d_fold = nullptr;  // per-key k_rsa_pow fold matrices (~101 KB each)
-  std::mutex mu;
-  // verify scratch
-  DevBuf digest, ts, hash_off, hash_len, flags, count, cursor, total, perm, xbuf, dedup, lead;
-  // host-path device copies
-  DevBuf dev_in, dev_out;
-  PinnedBuf pin_in, pin_out;
-  hipStream_t s_in = nullptr, s_out = nullptr;  // host-path copy streams
-  hipStream_t aux = nullptr;                     // grant prep (high priority), beside k_rsa_pow
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  ScratchOrder order;  // over digest / perm / xbuf / the decode and encode buffers
-  std::vector<hipEvent_t> chunk_ev;              // host-path chunk hand-offs
-  std::vector<hipEvent_t> tot_ev;                // wire host path: per-chunk decode totals on the host
-  // two sets of the host-path call's span events: a call records into one while
-  // the other keeps the last completed call's, read only when asked
-  hipEvent_t evs[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-  hipEvent_t* ev = evs[0];   // the set of the call in progress
-  int ev_set = 0, ev_done = 0;  // ev's set; the last completed call's
-  float last_ms[3] = {0, 0, 0};  // first upload, compute span, last download of the last host-path call
-  float last_total_ms = 0;       // whole pipelined host-path call (first H2D start -> last D2H end)
-  bool timing_pending = false;   // ev[0..3] recorded, last_ms not yet read from them (resolve_timing)
-  uint32_t chunk_grants = 0;     // host-path chunk target (grants), mochi_ctx_set_chunk_grants
-  uint32_t small_grants = 4096;  // small-batch launch sequence up to this many grants (mochi_ctx_set_small_batch)
-  // Write2 wire path: server-id table + decode scratch
-  DevBuf ids, id_off;
-  uint32_t n_ids = 0;
-  std::vector<std::string> server_ids;  // host copy for the fallback decoder (w2_host.cpp)
-  DevBuf w2_cnt, w2_status, w2_scan, w2_goff, w2_glen, w2_sig, w2_signer, w2_gkey, w2_okey, w2_oflags, w2_sigsrc,
-      w2_mgo, w2_ots, w2_okoff, w2_oklen, w2_same;
-  PinnedBuf w2_tot;
-  hipEvent_t ev_tot = nullptr;
-  EncState w2e;  // Write2 encoder (w2_encode.hip); its total is the wire size
-  // the last host-path call's certificate accept bitmap on the device (a slice
-  // of dev_out, valid until the next call on this context; nullptr when the
-  // device copy is not the final verdict, e.g. after host fallback decisions):
-  // multi.cpp all-gathers it in place of re-uploading the host bits
-  const uint32_t* acc_dev = nullptr;
-  uint32_t acc_words = 0;
-  uint64_t gen = 0;  // bumped (under mu) by every call that may rewrite dev_out / scratch
-  // per-stage profiling (mochi_ctx_set_profiling): one event set per verify call
-  bool profiling = false;
-  std::vector<std::vector<hipEvent_t>> prof_sets;
-};
-
 namespace mochi {
 // batcher.cpp: a batcher holds each of its contexts from create to its free
 void ctx_hold(mochi_ctx* c) {
@@ -459,15 +245,12 @@ int ctx_copy_accept_dev(mochi_ctx* c, uint64_t gen, int device, uint32_t* dst, u
 }
 }  // namespace mochi
 
-namespace {
-// every entry point that launches on the context's buffers, with c->mu held
-void new_call(mochi_ctx* c) {
+void mochi::new_call(mochi_ctx* c) {
   c->gen++;
   c->acc_dev = nullptr;
   c->acc_words = 0;
   mochi::t_ctx_gen = c->gen;
 }
-}  // namespace
 
 extern "C" {
 
@@ -528,9 +311,8 @@ mochi_ctx* mochi_ctx_create(int device, const uint8_t* moduli_be, uint32_t n_key
   c->device = device;
   c->n_keys = n_keys;
   c->chunk_grants = default_chunk_grants();
-  int save = 0;
-  (void)hipGetDevice(&save);
-  bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+  DeviceGuard dev(device);
+  bool ok = dev.ok && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking) == hipSuccess &&
             create_prep_stream(&c->aux) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
@@ -543,7 +325,6 @@ mochi_ctx* mochi_ctx_create(int device, const uint8_t* moduli_be, uint32_t n_key
             hipMalloc(&c->d_fold, sizeof(mochi::FoldKey) * n_keys) == hipSuccess &&
             hipMemcpy(c->d_fold, fold.data(), sizeof(mochi::FoldKey) * n_keys, hipMemcpyHostToDevice) == hipSuccess;
   for (int i = 0; i < 8 && ok; i++) ok = hipEventCreate(&c->evs[i / 4][i % 4]) == hipSuccess;
-  (void)hipSetDevice(save);
   if (!ok) {
     fail(MOCHI_EHIP, "context setup failed on device %d", device);
     mochi_ctx_destroy(c);
@@ -568,9 +349,7 @@ void mochi_ctx_destroy(mochi_ctx* c) {
 }  // extern "C"
 
 void mochi::ctx_free(mochi_ctx* c) {
-  int save = 0;
-  (void)hipGetDevice(&save);
-  (void)hipSetDevice(c->device);
+  DeviceGuard dev(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->s_out) (void)hipStreamSynchronize(c->s_out);
   for (auto& set : c->evs)
@@ -590,10 +369,9 @@ void mochi::ctx_free(mochi_ctx* c) {
   if (c->d_fold) (void)hipFree(c->d_fold);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
-  (void)hipSetDevice(save);
 }
 
-namespace {
+namespace mochi {
 
 int check_batch_header(const mochi_ctx* c, const mochi_batch* b, const mochi_params* p, const mochi_verdicts* o) {
   if (!c || !b || !p || !o) return fail(MOCHI_EINVAL, "null argument");
@@ -614,42 +392,6 @@ int check_batch_header(const mochi_ctx* c, const mochi_batch* b, const mochi_par
   return MOCHI_OK;
 }
 
-// Host-side consistency checks (host path only; the device path trusts the caller's device arrays).
-int check_batch_host(const mochi_batch* b) {
-  if (b->cert_grant_off[0] != 0 || b->cert_grant_off[b->n_certs] != b->n_grants)
-    return fail(MOCHI_EINVAL, "cert_grant_off must start at 0 and end at n_grants");
-  if (b->cert_op_off[0] != 0 || b->cert_op_off[b->n_certs] != b->n_ops)
-    return fail(MOCHI_EINVAL, "cert_op_off must start at 0 and end at n_ops");
-  for (uint32_t c = 0; c < b->n_certs; c++) {
-    if (b->cert_grant_off[c + 1] < b->cert_grant_off[c] || b->cert_op_off[c + 1] < b->cert_op_off[c])
-      return fail(MOCHI_EINVAL, "CSR offsets must be non-decreasing (cert %u)", c);
-    if (b->cert_op_off[c + 1] - b->cert_op_off[c] > MOCHI_MAX_OPS_PER_CERT)
-      return fail(MOCHI_EINVAL, "cert %u has more than %d ops", c, MOCHI_MAX_OPS_PER_CERT);
-  }
-  for (uint32_t i = 0; i < b->n_grants; i++) {
-    if (b->grant_len[i] > 65536) return fail(MOCHI_EINVAL, "grant %u longer than 65536 bytes", i);
-    if (b->grant_off[i] > b->grant_bytes_len || b->grant_len[i] > b->grant_bytes_len - b->grant_off[i])
-      return fail(MOCHI_EINVAL, "grant %u lies outside grant_bytes", i);
-  }
-  for (uint32_t o = 0; o < b->n_ops; o++) {
-    if (b->op_key[o] >= MOCHI_MAX_OPS_PER_CERT) return fail(MOCHI_EINVAL, "op_key[%u] >= %d", o, MOCHI_MAX_OPS_PER_CERT);
-    if (b->op_key_off && (b->op_key_off[o] > b->grant_bytes_len || b->op_key_len[o] > b->grant_bytes_len - b->op_key_off[o]))
-      return fail(MOCHI_EINVAL, "op key %u lies outside grant_bytes", o);
-  }
-  if (b->cert_mg_off) {
-    if (b->cert_mg_off[0] != 0 || b->cert_mg_off[b->n_certs] != b->n_mgs)
-      return fail(MOCHI_EINVAL, "cert_mg_off must start at 0 and end at n_mgs");
-    if (b->mg_grant_off[0] != 0 || b->mg_grant_off[b->n_mgs] != b->n_grants)
-      return fail(MOCHI_EINVAL, "mg_grant_off must start at 0 and end at n_grants");
-    for (uint32_t m = 0; m < b->n_mgs; m++)
-      if (b->mg_grant_off[m + 1] < b->mg_grant_off[m]) return fail(MOCHI_EINVAL, "mg_grant_off decreases at %u", m);
-    for (uint32_t c = 0; c < b->n_certs; c++)
-      if (b->cert_mg_off[c + 1] < b->cert_mg_off[c] || b->mg_grant_off[b->cert_mg_off[c]] != b->cert_grant_off[c])
-        return fail(MOCHI_EINVAL, "MultiGrants of cert %u do not cover its grants", c);
-  }
-  return MOCHI_OK;
-}
-
 // The last host-path call's spans, from its events (recorded during the call,
 // read only when asked).
 void resolve_timing(mochi_ctx* c) {
@@ -662,15 +404,8 @@ void resolve_timing(mochi_ctx* c) {
   (void)hipEventElapsedTime(&c->last_total_ms, e[0], e[3]);
 }
 
-// Scratch ordering across calls and streams (ScratchOrder).
-hipError_t scratch_acquire(mochi_ctx* c, hipStream_t st) { return c->order.acquire(st); }
-hipError_t scratch_release(mochi_ctx* c, hipStream_t st) { return c->order.release(st); }
-
-int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C);
-
 int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o, hipStream_t st,
-               const uint32_t* op_out_off = nullptr, const uint32_t* grant_same = nullptr,
-               const uint8_t* msg_status = nullptr) {
+               const uint32_t* op_out_off, const uint32_t* grant_same, const uint8_t* msg_status) {
   const uint32_t N = b->n_grants, C = b->n_certs;
   const uint64_t slots = mochi::slot_capacity(N, c->n_keys);
   if (slots > 0xFFFFFFF0ull) return fail(MOCHI_EINVAL, "batch too large");
@@ -744,47 +479,6 @@ int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_
   return MOCHI_OK;
 }
 
-// ---- host path: chunked H2D / compute / D2H pipeline ------------------------
-//
-// The batch is cut at certificate boundaries (multiples of 32 certificates, so
-// every chunk's accept bits start on a word) into chunks of ~kChunkGrants
-// grants.  Chunk j's inputs go up on the copy-in stream, its kernels run on the
-// context stream once they have landed, and its verdicts come down on the
-// copy-out stream while chunk j+1 computes.  Every chunk has its own input
-// region on the device and writes disjoint output slices, so the only
-// cross-stream ordering is one event per hand-off.  Sources that are already
-// pinned (mochi_host_alloc) are DMA'd in place; others are staged through the
-// context's pinned buffer with a parallel memcpy.
-bool is_pinned(const void* ptr) {
-  if (!ptr) return false;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
-}
-
-void par_memcpy(void* dst, const void* src, size_t n) {
-  constexpr size_t kPar = 8u << 20;
-  if (n < kPar) {
-    memcpy(dst, src, n);
-    return;
-  }
-  const unsigned hw = std::thread::hardware_concurrency();
-  const unsigned nt = hw < 2 ? 1 : hw > 8 ? 8 : hw;
-  const size_t per = (n + nt - 1) / nt;
-  std::vector<std::thread> th;
-  for (unsigned t = 1; t < nt; t++) {
-    const size_t lo = t * per;
-    if (lo >= n) break;
-    const size_t len = per < n - lo ? per : n - lo;
-    th.emplace_back([=] { memcpy((char*)dst + lo, (const char*)src + lo, len); });
-  }
-  memcpy(dst, src, per < n ? per : n);
-  for (auto& x : th) x.join();
-}
-
 // Verify scratch for N grants of C certificates: per grant (ts, flags, rare,
 // lead), per distinct prep result (N + C: digest, hash slice), per slot (perm, z).
 int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C) {
@@ -799,241 +493,6 @@ int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C) {
       (rc = c->total.ensure(mochi::kTotalWords * sizeof(uint32_t))) || (rc = c->perm.ensure(sizeof(uint32_t) * (size_t)slots)) ||
       (rc = c->xbuf.ensure(sizeof(uint32_t) * mochi::kL * (size_t)slots)))
     return rc;
-  return MOCHI_OK;
-}
-
-// Input segments of one chunk, in mochi_batch order.  The CSR arrays (6, 7,
-// 11, 12) are rebased per chunk and therefore always staged.
-enum Seg {
-  kBlob, kGrantOff, kGrantLen, kSig, kSigner, kGrantKey, kCertGrantOff, kCertOpOff, kOpKey, kOpFlags, kExpHash,
-  kCertMgOff, kMgGrantOff, kOpObjTs, kOpKeyOff, kOpKeyLen, kNumSeg
-};
-
-int run_host_pipeline(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o) {
-  const uint32_t N = b->n_grants, C = b->n_certs, O = b->n_ops;
-  c->acc_dev = nullptr;
-  c->acc_words = 0;
-  const bool mg = b->cert_mg_off != nullptr;
-  // --- plan chunks ---
-  struct Chunk {
-    uint32_t c0, c1, g0, g1, o0, o1, m0, m1;
-    uint64_t lo, hi;  // byte range [lo, hi) of grant_bytes this chunk reads
-    size_t seg[kNumSeg];
-  };
-  std::vector<Chunk> ch;
-  uint32_t max_grants = 0, max_certs = 0;
-  for (uint32_t c0 = 0; c0 < C || (C == 0 && ch.empty());) {
-    uint32_t c1 = c0;
-    do c1 = c1 + 32 < C ? c1 + 32 : C;
-    while (c1 < C && b->cert_grant_off[c1] - b->cert_grant_off[c0] < c->chunk_grants);
-    Chunk k{};
-    k.c0 = c0;
-    k.c1 = c1;
-    k.g0 = b->cert_grant_off[c0];
-    k.g1 = b->cert_grant_off[c1];
-    k.o0 = b->cert_op_off[c0];
-    k.o1 = b->cert_op_off[c1];
-    k.m0 = mg ? b->cert_mg_off[c0] : 0;
-    k.m1 = mg ? b->cert_mg_off[c1] : 0;
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (uint32_t g = k.g0; g < k.g1; g++) {
-      lo = b->grant_off[g] < lo ? b->grant_off[g] : lo;
-      const uint64_t e = b->grant_off[g] + b->grant_len[g];
-      hi = e > hi ? e : hi;
-    }
-    if (b->op_key_off)  // MOCHI_Q_BIND reads the op keys from the blob too
-      for (uint32_t x = k.o0; x < k.o1; x++) {
-        lo = b->op_key_off[x] < lo ? b->op_key_off[x] : lo;
-        const uint64_t e = b->op_key_off[x] + b->op_key_len[x];
-        hi = e > hi ? e : hi;
-      }
-    if (lo == UINT64_MAX) lo = hi = 0;  // nothing read from the blob
-    k.lo = lo;
-    k.hi = hi;
-    if (k.g1 - k.g0 > max_grants) max_grants = k.g1 - k.g0;
-    if (k.c1 - k.c0 > max_certs) max_certs = k.c1 - k.c0;
-    ch.push_back(k);
-    if (C == 0) break;
-    c0 = c1;
-  }
-  const size_t nchunks = ch.size();
-  auto seg_bytes = [&](const Chunk& k, int i) -> size_t {
-    const size_t ng = k.g1 - k.g0, nc = k.c1 - k.c0, no = k.o1 - k.o0, nm = k.m1 - k.m0;
-    switch (i) {
-      case kBlob: return (size_t)(k.hi - k.lo);
-      case kGrantOff: return sizeof(uint64_t) * ng;
-      case kGrantLen: return sizeof(uint32_t) * ng;
-      case kSig: return (size_t)MOCHI_RSA_BYTES * ng;
-      case kSigner: return sizeof(uint16_t) * ng;
-      case kGrantKey: return ng;
-      case kCertGrantOff: case kCertOpOff: return sizeof(uint32_t) * (nc + 1);
-      case kOpKey: case kOpFlags: return no;
-      case kExpHash: return (size_t)MOCHI_TXN_HASH_BYTES * nc;
-      case kCertMgOff: return mg ? sizeof(uint32_t) * (nc + 1) : 0;
-      case kMgGrantOff: return mg ? sizeof(uint32_t) * (nm + 1) : 0;
-      case kOpObjTs: return b->op_object_ts ? sizeof(int64_t) * no : 0;
-      case kOpKeyOff: return b->op_key_off ? sizeof(uint64_t) * no : 0;
-      default: return b->op_key_len ? sizeof(uint32_t) * no : 0;
-    }
-  };
-  auto seg_src = [&](const Chunk& k, int i) -> const void* {
-    switch (i) {
-      case kBlob: return b->grant_bytes + k.lo;
-      case kGrantOff: return b->grant_off + k.g0;
-      case kGrantLen: return b->grant_len + k.g0;
-      case kSig: return b->sig + (size_t)MOCHI_RSA_BYTES * k.g0;
-      case kSigner: return b->signer + k.g0;
-      case kGrantKey: return b->grant_key + k.g0;
-      case kOpKey: return b->op_key + k.o0;
-      case kOpFlags: return b->op_flags + k.o0;
-      case kExpHash: return b->expected_hash + (size_t)MOCHI_TXN_HASH_BYTES * k.c0;
-      case kOpObjTs: return b->op_object_ts ? b->op_object_ts + k.o0 : nullptr;
-      case kOpKeyOff: return b->op_key_off ? b->op_key_off + k.o0 : nullptr;
-      case kOpKeyLen: return b->op_key_len ? b->op_key_len + k.o0 : nullptr;
-      default: return nullptr;  // rebased CSR, always staged
-    }
-  };
-  auto rebased = [](int i) { return i == kCertGrantOff || i == kCertOpOff || i == kCertMgOff || i == kMgGrantOff; };
-  size_t in_total = 0;
-  for (auto& k : ch)
-    for (int i = 0; i < kNumSeg; i++) {
-      k.seg[i] = in_total;
-      in_total = align_up(in_total + seg_bytes(k, i), 256);
-    }
-  // --- output layout: whole-batch slices ---
-  const size_t nbits_g = ((size_t)N + 31) / 32 * 4, nbits_c = ((size_t)C + 31) / 32 * 4;
-  size_t out_total = 0;
-  auto take = [&](size_t bytes) {
-    const size_t off = out_total;
-    out_total = align_up(out_total + bytes, 256);
-    return off;
-  };
-  const size_t o_flags = take(N), o_ts = take(o->grant_ts ? sizeof(int64_t) * N : 0), o_acc = take(nbits_c),
-               o_reason = take(o->cert_reason ? C : 0), o_fail = take(o->cert_fail_op ? C : 0),
-               o_gbits = take(o->grant_valid_bits ? nbits_g : 0), o_dec = take(o->op_decision ? O : 0),
-               o_g0 = take(o->op_g0 ? sizeof(uint32_t) * O : 0), o_ots = take(o->op_ts ? sizeof(int64_t) * O : 0);
-  int rc;
-  if ((rc = c->pin_in.ensure(in_total)) || (rc = c->dev_in.ensure(in_total)) || (rc = c->pin_out.ensure(out_total)) ||
-      (rc = c->dev_out.ensure(out_total)) || (rc = ensure_scratch(c, max_grants, max_certs)))
-    return rc;
-  while (c->chunk_ev.size() < 2 * nchunks) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->chunk_ev.push_back(e);
-  }
-  bool pinned[kNumSeg];
-  for (int i = 0; i < kNumSeg; i++) pinned[i] = !rebased(i) && is_pinned(seg_src(ch[0], i));
-  uint8_t* pin = (uint8_t*)c->pin_in.p;
-  uint8_t* din = c->dev_in.as<uint8_t>();
-  uint8_t* dout = c->dev_out.as<uint8_t>();
-  uint8_t* pout = (uint8_t*)c->pin_out.p;
-  hipStream_t st = c->stream;
-  c->ev_set ^= 1;  // this call's span events: the other set keeps the last call's
-  c->ev = c->evs[c->ev_set];
-  HIP_TRY(hipEventRecord(c->ev[0], c->s_in));
-  for (size_t j = 0; j < nchunks; j++) {
-    Chunk& k = ch[j];
-    // stage + upload
-    uint32_t* cg = (uint32_t*)(pin + k.seg[kCertGrantOff]);
-    uint32_t* co = (uint32_t*)(pin + k.seg[kCertOpOff]);
-    for (uint32_t x = k.c0; x <= k.c1; x++) {
-      cg[x - k.c0] = b->cert_grant_off[x] - k.g0;
-      co[x - k.c0] = b->cert_op_off[x] - k.o0;
-    }
-    if (mg) {
-      uint32_t* cm = (uint32_t*)(pin + k.seg[kCertMgOff]);
-      uint32_t* mo = (uint32_t*)(pin + k.seg[kMgGrantOff]);
-      for (uint32_t x = k.c0; x <= k.c1; x++) cm[x - k.c0] = b->cert_mg_off[x] - k.m0;
-      for (uint32_t x = k.m0; x <= k.m1; x++) mo[x - k.m0] = b->mg_grant_off[x] - k.g0;
-    }
-    for (int i = 0; i < kNumSeg; i++) {
-      const size_t n = seg_bytes(k, i);
-      if (!n) continue;
-      const void* src = pin + k.seg[i];
-      if (pinned[i]) src = seg_src(k, i);
-      else if (!rebased(i)) par_memcpy(pin + k.seg[i], seg_src(k, i), n);
-      HIP_TRY(hipMemcpyAsync(din + k.seg[i], src, n, hipMemcpyHostToDevice, c->s_in));
-    }
-    HIP_TRY(hipEventRecord(c->chunk_ev[2 * j], c->s_in));
-    // compute
-    HIP_TRY(hipStreamWaitEvent(st, c->chunk_ev[2 * j], 0));
-    if (j == 0) HIP_TRY(hipEventRecord(c->ev[1], st));
-    auto at = [&](int i) -> const void* { return seg_bytes(k, i) ? (const void*)(din + k.seg[i]) : nullptr; };
-    mochi_batch db;
-    memset(&db, 0, sizeof db);
-    db.n_grants = k.g1 - k.g0;
-    db.n_certs = k.c1 - k.c0;
-    db.n_ops = k.o1 - k.o0;
-    db.n_mgs = k.m1 - k.m0;
-    db.grant_bytes_len = k.hi;
-    db.grant_bytes = din + k.seg[kBlob] - k.lo;  // kernels add the absolute grant_off / op_key_off
-    db.grant_off = (const uint64_t*)(din + k.seg[kGrantOff]);
-    db.grant_len = (const uint32_t*)(din + k.seg[kGrantLen]);
-    db.sig = din + k.seg[kSig];
-    db.signer = (const uint16_t*)(din + k.seg[kSigner]);
-    db.grant_key = din + k.seg[kGrantKey];
-    db.cert_grant_off = (const uint32_t*)(din + k.seg[kCertGrantOff]);
-    db.cert_op_off = (const uint32_t*)(din + k.seg[kCertOpOff]);
-    db.op_key = din + k.seg[kOpKey];
-    db.op_flags = din + k.seg[kOpFlags];
-    db.expected_hash = din + k.seg[kExpHash];
-    db.cert_mg_off = (const uint32_t*)at(kCertMgOff);
-    db.mg_grant_off = (const uint32_t*)at(kMgGrantOff);
-    db.op_object_ts = (const int64_t*)at(kOpObjTs);
-    db.op_key_off = (const uint64_t*)at(kOpKeyOff);
-    db.op_key_len = (const uint32_t*)at(kOpKeyLen);
-    mochi_verdicts dv;
-    memset(&dv, 0, sizeof dv);
-    dv.grant_flags = dout + o_flags + k.g0;
-    dv.grant_ts = o->grant_ts ? (int64_t*)(dout + o_ts) + k.g0 : nullptr;
-    dv.cert_accept_bits = (uint32_t*)(dout + o_acc) + k.c0 / 32;
-    dv.cert_reason = o->cert_reason ? dout + o_reason + k.c0 : nullptr;
-    dv.cert_fail_op = o->cert_fail_op ? dout + o_fail + k.c0 : nullptr;
-    dv.op_decision = o->op_decision ? dout + o_dec + k.o0 : nullptr;
-    dv.op_g0 = o->op_g0 ? (uint32_t*)(dout + o_g0) + k.o0 : nullptr;
-    dv.op_ts = o->op_ts ? (int64_t*)(dout + o_ots) + k.o0 : nullptr;
-    if ((rc = run_device(c, &db, p, &dv, st))) return rc;
-    if (j + 1 == nchunks && o->grant_valid_bits && N)
-      HIP_TRY(mochi::launch_pack_bits(dout + o_flags, N, MOCHI_GRANT_SIG_OK, (uint32_t*)(dout + o_gbits), st));
-    if (j + 1 == nchunks) HIP_TRY(hipEventRecord(c->ev[2], st));
-    HIP_TRY(hipEventRecord(c->chunk_ev[2 * j + 1], st));
-    // download this chunk's verdict slices
-    HIP_TRY(hipStreamWaitEvent(c->s_out, c->chunk_ev[2 * j + 1], 0));
-    auto down = [&](size_t off, size_t bytes) -> hipError_t {
-      return bytes ? hipMemcpyAsync(pout + off, dout + off, bytes, hipMemcpyDeviceToHost, c->s_out) : hipSuccess;
-    };
-    if (nchunks == 1 && out_total <= (4u << 20)) {  // one small chunk: one download of the whole region
-      HIP_TRY(down(0, out_total));
-      continue;
-    }
-    const size_t ng = k.g1 - k.g0, nc = k.c1 - k.c0, no = k.o1 - k.o0;
-    const size_t acc_words = j + 1 == nchunks ? nbits_c / 4 - k.c0 / 32 : nc / 32;
-    if (o->grant_flags) HIP_TRY(down(o_flags + k.g0, ng));
-    if (o->grant_ts) HIP_TRY(down(o_ts + sizeof(int64_t) * k.g0, sizeof(int64_t) * ng));
-    HIP_TRY(down(o_acc + 4 * (size_t)(k.c0 / 32), 4 * acc_words));
-    if (o->cert_reason) HIP_TRY(down(o_reason + k.c0, nc));
-    if (o->cert_fail_op) HIP_TRY(down(o_fail + k.c0, nc));
-    if (o->op_decision) HIP_TRY(down(o_dec + k.o0, no));
-    if (o->op_g0) HIP_TRY(down(o_g0 + sizeof(uint32_t) * k.o0, sizeof(uint32_t) * no));
-    if (o->op_ts) HIP_TRY(down(o_ots + sizeof(int64_t) * k.o0, sizeof(int64_t) * no));
-    if (j + 1 == nchunks && o->grant_valid_bits) HIP_TRY(down(o_gbits, nbits_g));
-  }
-  HIP_TRY(hipEventRecord(c->ev[3], c->s_out));
-  if (hipStreamSynchronize(c->s_out) != hipSuccess)
-    return fail(MOCHI_EHIP, "stream sync failed: %s", hipGetErrorString(hipGetLastError()));
-  // first upload (not overlapped), compute span, last download (not overlapped),
-  // whole call: read from the events when asked (resolve_timing)
-  c->ev_done = c->ev_set;
-  c->timing_pending = true;
-  void* dsts[] = {o->grant_flags, o->grant_ts, o->cert_accept_bits, o->cert_reason, o->cert_fail_op,
-                  o->grant_valid_bits, o->op_decision, o->op_g0, o->op_ts};
-  const size_t offs[] = {o_flags, o_ts, o_acc, o_reason, o_fail, o_gbits, o_dec, o_g0, o_ots};
-  const size_t lens[] = {(size_t)N, sizeof(int64_t) * N, nbits_c, (size_t)C, (size_t)C, nbits_g,
-                         (size_t)O, sizeof(uint32_t) * O, sizeof(int64_t) * O};
-  for (int i = 0; i < 9; i++)
-    if (dsts[i] && lens[i]) memcpy(dsts[i], pout + offs[i], lens[i]);
-  c->acc_dev = (const uint32_t*)(dout + o_acc);
-  c->acc_words = (uint32_t)(nbits_c / 4);
   return MOCHI_OK;
 }
 
@@ -1092,7 +551,7 @@ int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, uint32_
 
 // Grow a decode buffer; if it must be reallocated, first let the stream drain
 // (an earlier chunk's kernels may still read the old allocation).
-int grow(DevBuf& b, size_t bytes, hipStream_t st) {
+static int grow(DevBuf& b, size_t bytes, hipStream_t st) {
   if (bytes <= b.cap) return MOCHI_OK;
   HIP_TRY(hipStreamSynchronize(st));
   return b.ensure(bytes);
@@ -1177,8 +636,8 @@ int w2_verify(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, 
 }
 
 // Device-resident wire batch, one shot (mochi_verify_write2_device).
-int run_write2_device(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                      uint8_t* status, hipStream_t st) {
+static int run_write2_device(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
+                             uint8_t* status, hipStream_t st) {
   const uint32_t M = w->n_msgs;
   if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
   int rc;
@@ -1213,7 +672,7 @@ int check_write2_header(const mochi_ctx* c, const mochi_write2_batch* w, const m
   return MOCHI_OK;
 }
 
-}  // namespace
+}  // namespace mochi
 
 extern "C" {
 
@@ -1222,27 +681,10 @@ int mochi_verify_batch_device(mochi_ctx* c, const mochi_batch* b, const mochi_pa
   int rc = check_batch_header(c, b, p, o);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(c->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   new_call(c);
-  rc = run_device(c, b, p, o, (hipStream_t)stream);  // NULL = the null stream, as in HIP
-  (void)hipSetDevice(save);
-  return rc;
-}
-
-int mochi_verify_batch(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o) {
-  int rc = check_batch_header(c, b, p, o);
-  if (rc) return rc;
-  if ((rc = check_batch_host(b))) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
-  new_call(c);
-  rc = run_host_pipeline(c, b, p, o);
-  (void)hipSetDevice(save);
-  return rc;
+  return run_device(c, b, p, o, (hipStream_t)stream);  // NULL = the null stream, as in HIP
 }
 
 void* mochi_host_alloc(uint64_t bytes) {
@@ -1287,9 +729,8 @@ int mochi_ctx_set_server_ids(mochi_ctx* c, const uint8_t* ids, const uint32_t* i
     if (id_off[i + 1] < id_off[i] || id_off[i + 1] - id_off[i] > 256)
       return fail(MOCHI_EINVAL, "server id %u: bad length", i);
   std::lock_guard<std::mutex> lk(c->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   const size_t nb = id_off[n_ids];
   int rc = c->ids.ensure(nb ? nb : 1);
   if (!rc) rc = c->id_off.ensure(4 * ((size_t)n_ids + 1));
@@ -1301,7 +742,6 @@ int mochi_ctx_set_server_ids(mochi_ctx* c, const uint8_t* ids, const uint32_t* i
     c->server_ids.clear();
     for (uint32_t i = 0; i < n_ids; i++) c->server_ids.emplace_back((const char*)ids + id_off[i], id_off[i + 1] - id_off[i]);
   }
-  (void)hipSetDevice(save);
   return rc;
 }
 
@@ -1310,55 +750,10 @@ int mochi_verify_write2_device(mochi_ctx* c, const mochi_write2_batch* w, const 
   int rc = check_write2_header(c, w, p, o);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(c->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   new_call(c);
-  rc = run_write2_device(c, w, p, o, msg_status, (hipStream_t)stream);
-  (void)hipSetDevice(save);
-  return rc;
-}
-
-static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                              uint8_t* msg_status, mochi_write2_decoded* dec);
-
-int mochi_verify_write2(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                        uint8_t* msg_status) {
-  int rc = check_write2_header(c, w, p, o);
-  if (rc) return rc;
-  return verify_write2_host(c, w, p, o, msg_status, nullptr);
-}
-
-int mochi_write2_decode(mochi_ctx* c, const mochi_write2_batch* w, mochi_write2_decoded* out) {
-  if (!out) return fail(MOCHI_EINVAL, "null argument");
-  memset(out, 0, sizeof *out);
-  mochi_params p = {1, 1, 0, 0};
-  mochi_verdicts o;
-  memset(&o, 0, sizeof o);
-  uint32_t dummy = 0;
-  o.cert_accept_bits = &dummy;
-  int rc = check_write2_header(c, w, &p, &o);
-  if (rc) return rc;
-  return verify_write2_host(c, w, &p, &o, nullptr, out);
-}
-
-void mochi_write2_decoded_free(mochi_write2_decoded* d) {
-  if (!d) return;
-  free(d->grant_off);
-  free(d->grant_len);
-  free(d->sig);
-  free(d->signer);
-  free(d->grant_key);
-  free(d->cert_grant_off);
-  free(d->cert_op_off);
-  free(d->op_key);
-  free(d->op_flags);
-  free(d->msg_status);
-  free(d->cert_mg_off);
-  free(d->mg_grant_off);
-  free(d->op_key_off);
-  free(d->op_key_len);
-  memset(d, 0, sizeof *d);
+  return run_write2_device(c, w, p, o, msg_status, (hipStream_t)stream);
 }
 
 // ---- Write2 encode (client certificate assembly) ----------------------------
@@ -1455,420 +850,6 @@ int mochi_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8
   return run_write2_encode_device(c, s, wire, wire_cap, msg_off, msg_len, status, wire_len, (hipStream_t)stream);
 }
 
-// ---- Write2 wire path: the messages the device decoder declines -------------
-//
-// MOCHI_MSG_FALLBACK messages (repeated / merged fields, non-canonical Grant
-// bytes, more than 32 MultiGrants or 64 grants per MultiGrant) are decoded on
-// the host with full protobuf-java semantics (w2_host.cpp) into an SoA batch and
-// verified through the same device path as every other certificate; their
-// verdicts replace the UNDECIDED placeholder.  Messages the host decoder cannot
-// express (more than MOCHI_MAX_OPS_PER_CERT operations, a grant over 64 KiB,
-// op_flags_off disagreeing with the operation count) stay UNDECIDED.
-static int decide_fallback(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                           const std::vector<uint32_t>& msgs) {
-  const uint32_t* ofo = w->op_flags_off;
-  std::vector<uint32_t> take;
-  std::vector<mochi_host::Message> dec;
-  for (uint32_t m : msgs) {
-    mochi_host::Message d;
-    if (mochi_host::decode_full(w->wire + w->msg_off[m], w->msg_len[m], c->server_ids, d) != MOCHI_MSG_OK) continue;
-    if (ofo && ofo[m + 1] - ofo[m] != d.ops.size()) continue;
-    bool fits = true;
-    for (auto& mg : d.mgs)
-      for (auto& g : mg.grants) fits &= g.bytes.size() <= 65536;
-    if (!fits) continue;
-    take.push_back(m);
-    dec.push_back(std::move(d));
-  }
-  if (take.empty()) return MOCHI_OK;
-  std::vector<uint8_t> blob, sig, gkey, opk, opf, hashes;
-  std::vector<uint64_t> goff, okoff;
-  std::vector<uint32_t> glen, cgo{0}, coo{0}, cmo{0}, mgo{0}, oklen;
-  std::vector<uint16_t> signer;
-  std::vector<int64_t> ots;
-  for (size_t i = 0; i < take.size(); i++) {
-    const uint32_t m = take[i];
-    const mochi_host::Message& d = dec[i];
-    for (auto& mg : d.mgs) {
-      for (auto& g : mg.grants) {
-        goff.push_back(blob.size());
-        glen.push_back((uint32_t)g.bytes.size());
-        blob.insert(blob.end(), g.bytes.begin(), g.bytes.end());
-        sig.insert(sig.end(), g.sig, g.sig + MOCHI_RSA_BYTES);
-        signer.push_back(mg.signer);
-        gkey.push_back(g.slot);
-      }
-      mgo.push_back((uint32_t)goff.size());
-    }
-    cmo.push_back((uint32_t)mgo.size() - 1);
-    cgo.push_back((uint32_t)goff.size());
-    for (size_t j = 0; j < d.ops.size(); j++) {
-      const auto& op = d.ops[j];
-      opk.push_back(op.slot);
-      const uint8_t fl = ofo ? w->op_flags[ofo[m] + j] : (uint8_t)(MOCHI_OP_LOCAL | MOCHI_OP_HAS_SVOC);
-      opf.push_back((uint8_t)(fl | (op.not_write ? MOCHI_OP_NOT_WRITE : 0)));
-      ots.push_back(ofo && w->op_object_ts ? w->op_object_ts[ofo[m] + j] : 0);
-      okoff.push_back(blob.size());
-      oklen.push_back((uint32_t)op.key_bytes.size());
-      blob.insert(blob.end(), op.key_bytes.begin(), op.key_bytes.end());
-    }
-    coo.push_back((uint32_t)opk.size());
-    hashes.insert(hashes.end(), w->expected_hash + (size_t)m * MOCHI_TXN_HASH_BYTES,
-                  w->expected_hash + (size_t)(m + 1) * MOCHI_TXN_HASH_BYTES);
-  }
-  if (blob.empty()) blob.push_back(0);
-  mochi_batch b;
-  memset(&b, 0, sizeof b);
-  b.n_grants = (uint32_t)goff.size();
-  b.n_certs = (uint32_t)take.size();
-  b.n_ops = (uint32_t)opk.size();
-  b.n_mgs = (uint32_t)mgo.size() - 1;
-  b.grant_bytes_len = blob.size();
-  b.grant_bytes = blob.data();
-  b.grant_off = goff.data();
-  b.grant_len = glen.data();
-  b.sig = sig.data();
-  b.signer = signer.data();
-  b.grant_key = gkey.data();
-  b.cert_grant_off = cgo.data();
-  b.cert_op_off = coo.data();
-  b.op_key = opk.data();
-  b.op_flags = opf.data();
-  b.expected_hash = hashes.data();
-  b.cert_mg_off = cmo.data();
-  b.mg_grant_off = mgo.data();
-  b.op_object_ts = ots.data();
-  b.op_key_off = okoff.data();
-  b.op_key_len = oklen.data();
-  const size_t C = take.size(), O = opk.size();
-  std::vector<uint32_t> acc((C + 31) / 32), og0(O + 1);
-  std::vector<uint8_t> reason(C), fail(C), odec(O + 1);
-  std::vector<int64_t> ots_out(O + 1);
-  mochi_verdicts v;
-  memset(&v, 0, sizeof v);
-  v.cert_accept_bits = acc.data();
-  v.cert_reason = reason.data();
-  v.cert_fail_op = fail.data();
-  v.op_decision = odec.data();
-  v.op_g0 = og0.data();
-  v.op_ts = ots_out.data();
-  resolve_timing(c);
-  float saved[4] = {c->last_ms[0], c->last_ms[1], c->last_ms[2], c->last_total_ms};
-  const int rc = run_host_pipeline(c, &b, p, &v);
-  c->last_ms[0] = saved[0], c->last_ms[1] = saved[1], c->last_ms[2] = saved[2], c->last_total_ms = saved[3];
-  c->timing_pending = false;
-  if (rc) return rc;
-  for (size_t i = 0; i < C; i++) {
-    const uint32_t m = take[i];
-    const bool a = (acc[i >> 5] >> (i & 31)) & 1u;
-    if (a) o->cert_accept_bits[m >> 5] |= 1u << (m & 31);
-    else o->cert_accept_bits[m >> 5] &= ~(1u << (m & 31));
-    if (o->cert_reason) o->cert_reason[m] = reason[i];
-    if (o->cert_fail_op) o->cert_fail_op[m] = fail[i];
-    if (ofo)
-      for (uint32_t j = 0; j < coo[i + 1] - coo[i]; j++) {
-        const size_t src = coo[i] + j, dst = ofo[m] + j;
-        if (o->op_decision) o->op_decision[dst] = odec[src];
-        if (o->op_g0) o->op_g0[dst] = og0[src];
-        if (o->op_ts) o->op_ts[dst] = ots_out[src];
-      }
-  }
-  return MOCHI_OK;
-}
-
-// ---- Write2 wire path, host memory: chunked pipeline -------------------------
-//
-// Messages are cut into chunks of whole messages (multiples of 32, so each
-// chunk's accept bits start on a word) of ~chunk_grants * 256 wire bytes.
-// For chunk j:
-// stage + upload (copy-in stream), then on the context stream the decode count
-// phase and its totals; chunk j-2's emit + verify + fix-up is enqueued once ITS
-// totals are on the host, so the host waits only for count kernels while the
-// device verifies earlier chunks and the copy engines move the next one.
-// Verdicts come down per chunk on the copy-out stream.
-static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                              uint8_t* msg_status, mochi_write2_decoded* dec) {
-  constexpr size_t kW2Lag = 2;  // chunks counted ahead of the one being verified
-  int rc;
-  const uint32_t M = w->n_msgs;
-  for (uint32_t m = 0; m < M; m++)
-    if (w->msg_off[m] > w->wire_len || w->msg_len[m] > w->wire_len - w->msg_off[m])
-      return fail(MOCHI_EINVAL, "message %u lies outside wire", m);
-  if (w->op_flags_off) {  // the device trusts these offsets: validate them here
-    if (w->op_flags_off[0] != 0) return fail(MOCHI_EINVAL, "op_flags_off[0] must be 0");
-    for (uint32_t m = 0; m < M; m++)
-      if (w->op_flags_off[m + 1] < w->op_flags_off[m]) return fail(MOCHI_EINVAL, "op_flags_off decreases at %u", m);
-  }
-  if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
-  std::lock_guard<std::mutex> lk(c->mu);
-  new_call(c);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
-  struct Restore {
-    int d;
-    ~Restore() { (void)hipSetDevice(d); }
-  } restore{save};
-  const uint32_t* ofo = w->op_flags_off;
-  const size_t O_in = ofo ? ofo[M] : 0;
-  // --- chunks ---
-  struct Chunk {
-    uint32_t m0, m1;
-    uint64_t lo, hi;  // wire byte range
-    size_t seg[7], cnt;
-  };
-  std::vector<Chunk> ch;
-  // ~67 MB of wire bytes per chunk at the default chunk_grants (measured on one
-  // box, 250k messages: 45.5 GB/s at 67 MB, 43.5 at 134 MB, 40.3 at 34 MB; a
-  // ramp of smaller chunks at fill and drain measured 37.7: every chunk pays
-  // the verify path's latency floor, ~0.6 ms, whatever its size)
-  const uint64_t target = dec ? UINT64_MAX : (uint64_t)c->chunk_grants * 256;
-  for (uint32_t m0 = 0; m0 < M || ch.empty();) {
-    uint32_t m1 = m0;
-    uint64_t bytes = 0;
-    do {
-      const uint32_t next = m1 + 32 < M ? m1 + 32 : M;
-      for (uint32_t m = m1; m < next; m++) bytes += w->msg_len[m];
-      m1 = next;
-    } while (m1 < M && bytes < target);
-    Chunk k{};
-    k.m0 = m0;
-    k.m1 = m1;
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (uint32_t m = m0; m < m1; m++) {
-      lo = w->msg_off[m] < lo ? w->msg_off[m] : lo;
-      hi = w->msg_off[m] + w->msg_len[m] > hi ? w->msg_off[m] + w->msg_len[m] : hi;
-    }
-    if (lo == UINT64_MAX) lo = hi = 0;
-    k.lo = lo;
-    k.hi = hi;
-    ch.push_back(k);
-    if (M == 0) break;
-    m0 = m1;
-  }
-  const size_t nch = ch.size();
-  // --- input segments: wire slice, msg_off, msg_len, op_flags_off (rebased), op_flags, op_object_ts, hash ---
-  auto seg_bytes = [&](const Chunk& k, int i) -> size_t {
-    const size_t nm = k.m1 - k.m0, no = ofo ? ofo[k.m1] - ofo[k.m0] : 0;
-    switch (i) {
-      case 0: return (size_t)(k.hi - k.lo);
-      case 1: return 8 * nm;
-      case 2: return 4 * nm;
-      case 3: return ofo ? 4 * (nm + 1) : 0;
-      case 4: return ofo ? no : 0;
-      case 5: return ofo && w->op_object_ts ? 8 * no : 0;
-      default: return (size_t)MOCHI_TXN_HASH_BYTES * nm;
-    }
-  };
-  auto seg_src = [&](const Chunk& k, int i) -> const void* {
-    switch (i) {
-      case 0: return w->wire + k.lo;
-      case 1: return w->msg_off + k.m0;
-      case 2: return w->msg_len + k.m0;
-      case 3: return nullptr;  // rebased, staged
-      case 4: return ofo ? w->op_flags + ofo[k.m0] : nullptr;
-      case 5: return ofo && w->op_object_ts ? w->op_object_ts + ofo[k.m0] : nullptr;
-      default: return w->expected_hash + (size_t)MOCHI_TXN_HASH_BYTES * k.m0;
-    }
-  };
-  size_t in_total = 0, cnt_total = 0;
-  for (auto& k : ch) {
-    for (int i = 0; i < 7; i++) {
-      k.seg[i] = in_total;
-      in_total = align_up(in_total + seg_bytes(k, i), 256);
-    }
-    k.cnt = cnt_total;
-    cnt_total += mochi::w2_scratch_words(k.m1 - k.m0);
-  }
-  const size_t nbits = ((size_t)M + 31) / 32 * 4;
-  size_t out_total = 0;
-  auto take = [&](size_t bytes) {
-    const size_t off = out_total;
-    out_total = align_up(out_total + bytes, 256);
-    return off;
-  };
-  const size_t o_acc = take(nbits), o_reason = take(M), o_fail = take(M), o_status = take(M ? M : 1),
-               o_dec = take(o->op_decision ? O_in : 0), o_g0 = take(o->op_g0 ? 4 * O_in : 0),
-               o_ots = take(o->op_ts ? 8 * O_in : 0);
-  if ((rc = c->pin_in.ensure(in_total)) || (rc = c->dev_in.ensure(in_total)) || (rc = c->pin_out.ensure(out_total)) ||
-      (rc = c->dev_out.ensure(out_total)) || (rc = c->w2_cnt.ensure(4 * cnt_total)) ||
-      (rc = c->w2_tot.ensure(16 * nch)))
-    return rc;
-  while (c->chunk_ev.size() < 2 * nch) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->chunk_ev.push_back(e);
-  }
-  while (c->tot_ev.size() < nch) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->tot_ev.push_back(e);
-  }
-  uint8_t* pin = (uint8_t*)c->pin_in.p;
-  uint8_t* din = c->dev_in.as<uint8_t>();
-  uint8_t* dout = c->dev_out.as<uint8_t>();
-  uint8_t* pout = (uint8_t*)c->pin_out.p;
-  uint32_t* tot = (uint32_t*)c->w2_tot.p;
-  hipStream_t st = c->stream;
-  // sources already in pinned memory (mochi_host_alloc) are DMA'd in place;
-  // the rebased op_flags_off CSR (segment 3) is always staged
-  // One small chunk (a batcher flush): every segment staged and ONE upload and
-  // ONE download of the whole region -- a copy costs ~5 us of its own on the
-  // GPU whatever its size, and a 2-message batch moved 5 + 7 of them.
-  const bool one_copy = nch == 1 && in_total <= (4u << 20);
-  // ... and both copies on the launch stream: nothing to overlap them with, and
-  // a cross-stream hand-off is one more event record, wait and barrier packet
-  const bool on_st = one_copy && !copy_streams();  // MOCHI_COPY_STREAMS=1 (A/B): the copy streams anyway
-  hipStream_t s_in = on_st ? st : c->s_in, s_out = on_st ? st : c->s_out;
-  bool pinned[7];
-  for (int i = 0; i < 7; i++) pinned[i] = !one_copy && i != 3 && is_pinned(seg_src(ch[0], i));
-  std::vector<mochi_write2_batch> dws(nch);
-  std::vector<mochi::W2Args> args(nch);
-  HIP_TRY(scratch_acquire(c, st));
-  c->ev_set ^= 1;  // this call's span events: the other set keeps the last call's
-  c->ev = c->evs[c->ev_set];
-  HIP_TRY(hipEventRecord(c->ev[0], s_in));
-  // phase 2 + download of chunk j (its totals must be on the host)
-  auto finish = [&](size_t j) -> int {
-    Chunk& k = ch[j];
-    HIP_TRY(hipEventSynchronize(c->tot_ev[j]));
-    const uint32_t* t = tot + 4 * j;
-    const uint32_t nm = k.m1 - k.m0, o0 = ofo ? ofo[k.m0] : 0;
-    mochi_verdicts dv;
-    memset(&dv, 0, sizeof dv);
-    dv.cert_accept_bits = (uint32_t*)(dout + o_acc) + k.m0 / 32;
-    dv.cert_reason = dout + o_reason + k.m0;
-    dv.cert_fail_op = dout + o_fail + k.m0;
-    dv.op_decision = o->op_decision ? dout + o_dec + o0 : nullptr;
-    dv.op_g0 = o->op_g0 ? (uint32_t*)(dout + o_g0) + o0 : nullptr;
-    dv.op_ts = o->op_ts ? (int64_t*)(dout + o_ots) + o0 : nullptr;
-    int r = w2_verify(c, &dws[j], p, &dv, args[j], t[0], t[1], t[2], dws[j].op_flags_off, st, dec != nullptr);
-    if (r) return r;
-    if (dec) return MOCHI_OK;
-    if (j + 1 == nch) HIP_TRY(hipEventRecord(c->ev[2], st));
-    if (!on_st) {
-      HIP_TRY(hipEventRecord(c->chunk_ev[2 * j + 1], st));
-      HIP_TRY(hipStreamWaitEvent(s_out, c->chunk_ev[2 * j + 1], 0));
-    }
-    auto down = [&](size_t off, size_t bytes) -> hipError_t {
-      return bytes ? hipMemcpyAsync(pout + off, dout + off, bytes, hipMemcpyDeviceToHost, s_out) : hipSuccess;
-    };
-    if (one_copy) return (int)(down(0, out_total) == hipSuccess ? MOCHI_OK : fail(MOCHI_EHIP, "download failed"));
-    const size_t no = ofo ? ofo[k.m1] - o0 : 0;
-    const size_t acc_words = j + 1 == nch ? nbits / 4 - k.m0 / 32 : nm / 32;
-    HIP_TRY(down(o_acc + 4 * (size_t)(k.m0 / 32), 4 * acc_words));
-    HIP_TRY(down(o_reason + k.m0, nm));
-    HIP_TRY(down(o_fail + k.m0, nm));
-    HIP_TRY(down(o_status + k.m0, nm));
-    if (o->op_decision) HIP_TRY(down(o_dec + o0, no));
-    if (o->op_g0) HIP_TRY(down(o_g0 + 4 * (size_t)o0, 4 * no));
-    if (o->op_ts) HIP_TRY(down(o_ots + 8 * (size_t)o0, 8 * no));
-    return MOCHI_OK;
-  };
-  for (size_t j = 0; j < nch; j++) {
-    Chunk& k = ch[j];
-    const uint32_t nm = k.m1 - k.m0;
-    if (ofo) {
-      uint32_t* f = (uint32_t*)(pin + k.seg[3]);
-      for (uint32_t m = k.m0; m <= k.m1; m++) f[m - k.m0] = ofo[m] - ofo[k.m0];
-    }
-    size_t staged_end = 0;
-    for (int i = 0; i < 7; i++) {
-      const size_t n = seg_bytes(k, i);
-      if (!n) continue;
-      const void* src = pin + k.seg[i];
-      if (pinned[i]) src = seg_src(k, i);  // DMA'd in place (e.g. the batcher's pinned batch)
-      else if (i != 3) par_memcpy(pin + k.seg[i], seg_src(k, i), n);
-      if (one_copy) staged_end = k.seg[i] + n > staged_end ? k.seg[i] + n : staged_end;
-      else HIP_TRY(hipMemcpyAsync(din + k.seg[i], src, n, hipMemcpyHostToDevice, s_in));
-    }
-    if (one_copy && staged_end) HIP_TRY(hipMemcpyAsync(din, pin, staged_end, hipMemcpyHostToDevice, s_in));
-    if (!on_st) HIP_TRY(hipEventRecord(c->chunk_ev[2 * j], s_in));
-    mochi_write2_batch& dw = dws[j];
-    memset(&dw, 0, sizeof dw);
-    dw.n_msgs = nm;
-    dw.wire_len = k.hi;
-    dw.wire = din + k.seg[0] - k.lo;  // message offsets stay absolute
-    dw.msg_off = (const uint64_t*)(din + k.seg[1]);
-    dw.msg_len = (const uint32_t*)(din + k.seg[2]);
-    dw.op_flags_off = ofo ? (const uint32_t*)(din + k.seg[3]) : nullptr;
-    dw.op_flags = ofo ? din + k.seg[4] : nullptr;
-    dw.op_object_ts = seg_bytes(k, 5) ? (const int64_t*)(din + k.seg[5]) : nullptr;
-    dw.expected_hash = din + k.seg[6];
-    if (!on_st) HIP_TRY(hipStreamWaitEvent(st, c->chunk_ev[2 * j], 0));
-    if (j == 0) HIP_TRY(hipEventRecord(c->ev[1], st));
-    if ((rc = w2_count(c, &dw, dout + o_status + k.m0, c->w2_cnt.as<uint32_t>() + k.cnt, tot + 4 * j, c->tot_ev[j], st,
-                       &args[j])))
-      return rc;
-    // the verify of chunk j - kW2Lag: its totals are read on the host, so the
-    // host waits for its count; with two chunks of lag the stream still holds
-    // work while it waits
-    if (j >= kW2Lag && (rc = finish(j - kW2Lag))) return rc;
-  }
-  for (size_t j = nch > kW2Lag ? nch - kW2Lag : 0; j < nch; j++)
-    if ((rc = finish(j))) return rc;
-  HIP_TRY(scratch_release(c, st));
-  if (dec) {
-    // decode-only (one chunk): copy the decoded SoA back (tests / inspection)
-    const mochi::W2Args& da = args[0];
-    const uint32_t N = tot[0], O = tot[1], NM = tot[2];
-    dec->n_msgs = M;
-    dec->n_grants = N;
-    dec->n_ops = O;
-    dec->n_mgs = NM;
-    dec->grant_off = (uint64_t*)malloc(8 * (size_t)N + 8);
-    dec->grant_len = (uint32_t*)malloc(4 * (size_t)N + 4);
-    dec->sig = (uint8_t*)malloc((size_t)MOCHI_RSA_BYTES * N + 1);
-    dec->signer = (uint16_t*)malloc(2 * (size_t)N + 2);
-    dec->grant_key = (uint8_t*)malloc((size_t)N + 1);
-    dec->cert_grant_off = (uint32_t*)malloc(4 * ((size_t)M + 1));
-    dec->cert_op_off = (uint32_t*)malloc(4 * ((size_t)M + 1));
-    dec->op_key = (uint8_t*)malloc((size_t)O + 1);
-    dec->op_flags = (uint8_t*)malloc((size_t)O + 1);
-    dec->msg_status = (uint8_t*)malloc((size_t)M + 1);
-    dec->cert_mg_off = (uint32_t*)malloc(4 * ((size_t)M + 1));
-    dec->mg_grant_off = (uint32_t*)malloc(4 * ((size_t)NM + 1));
-    dec->op_key_off = (uint64_t*)malloc(8 * (size_t)O + 8);
-    dec->op_key_len = (uint32_t*)malloc(4 * (size_t)O + 4);
-    struct {
-      void* dst;
-      const void* src;
-      size_t n;
-    } cp[] = {{dec->grant_off, da.grant_off, 8 * (size_t)N},     {dec->grant_len, da.grant_len, 4 * (size_t)N},
-              {dec->sig, da.sig, (size_t)MOCHI_RSA_BYTES * N},   {dec->signer, da.signer, 2 * (size_t)N},
-              {dec->grant_key, da.grant_key, N},                 {dec->cert_grant_off, da.cert_grant_off, 4 * ((size_t)M + 1)},
-              {dec->cert_op_off, da.cert_op_off, 4 * ((size_t)M + 1)}, {dec->op_key, da.op_key, O},
-              {dec->op_flags, da.op_flags, O},                   {dec->msg_status, da.status, M},
-              {dec->cert_mg_off, da.cert_mg_off, 4 * ((size_t)M + 1)}, {dec->mg_grant_off, da.mg_grant_off, 4 * ((size_t)NM + 1)},
-              {dec->op_key_off, da.op_key_off, 8 * (size_t)O},   {dec->op_key_len, da.op_key_len, 4 * (size_t)O}};
-    for (auto& x : cp)
-      if (x.n) HIP_TRY(hipMemcpyAsync(x.dst, x.src, x.n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return MOCHI_OK;
-  }
-  HIP_TRY(hipEventRecord(c->ev[3], s_out));
-  HIP_TRY(hipStreamSynchronize(s_out));
-  c->ev_done = c->ev_set;
-  c->timing_pending = true;  // read from the events when asked (mochi_ctx_last_timing): four API calls off the call's path
-  std::vector<uint32_t> fallback;
-  for (uint32_t m = 0; m < M; m++)
-    if (pout[o_status + m] == MOCHI_MSG_FALLBACK) fallback.push_back(m);
-  memcpy(o->cert_accept_bits, pout + o_acc, nbits);
-  if (o->cert_reason) memcpy(o->cert_reason, pout + o_reason, M);
-  if (o->cert_fail_op) memcpy(o->cert_fail_op, pout + o_fail, M);
-  if (msg_status) memcpy(msg_status, pout + o_status, M);
-  if (o->op_decision) memcpy(o->op_decision, pout + o_dec, O_in);
-  if (o->op_g0) memcpy(o->op_g0, pout + o_g0, 4 * O_in);
-  if (o->op_ts) memcpy(o->op_ts, pout + o_ots, 8 * O_in);
-  c->acc_dev = (const uint32_t*)(dout + o_acc);
-  c->acc_words = (uint32_t)(nbits / 4);
-  if (fallback.empty()) return MOCHI_OK;
-  rc = decide_fallback(c, w, p, o, fallback);
-  c->acc_dev = nullptr;  // the host decided some verdicts (and the fallback batch reused dev_out)
-  c->acc_words = 0;
-  return rc;
-}
-
 int mochi_fold_matrix(const uint8_t* modulus_be, int8_t* img, uint32_t* cadd) {
   if (!modulus_be || !img || !cadd) return fail(MOCHI_EINVAL, "null argument");
   if (!(modulus_be[0] & 0x80) || !(modulus_be[255] & 1)) return fail(MOCHI_EINVAL, "modulus must be odd, 2048 bits");
@@ -1888,9 +869,8 @@ int mochi_rsa_public_op(mochi_ctx* c, uint32_t n, const uint8_t* sig_be, const u
   if (n == 0) return MOCHI_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   new_call(c);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(c->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   const uint64_t slots = mochi::slot_capacity(n, c->n_keys);
   const size_t sig_bytes = (size_t)MOCHI_RSA_BYTES * n, y_bytes = sizeof(uint32_t) * 64 * (size_t)n;
   int rc;
@@ -1898,10 +878,8 @@ int mochi_rsa_public_op(mochi_ctx* c, uint32_t n, const uint8_t* sig_be, const u
       (rc = c->digest.ensure(sizeof(uint32_t) * 8 * (size_t)n)) || (rc = c->flags.ensure(n)) ||
       (rc = c->count.ensure(sizeof(uint32_t) * c->n_keys)) || (rc = c->cursor.ensure(sizeof(uint32_t) * c->n_keys)) ||
       (rc = c->total.ensure(mochi::kTotalWords * sizeof(uint32_t))) || (rc = c->perm.ensure(sizeof(uint32_t) * (size_t)slots)) ||
-      (rc = c->xbuf.ensure(sizeof(uint32_t) * mochi::kL * (size_t)slots))) {
-    (void)hipSetDevice(save);
+      (rc = c->xbuf.ensure(sizeof(uint32_t) * mochi::kL * (size_t)slots)))
     return rc;
-  }
   hipStream_t st = c->stream;
   uint8_t* din = c->dev_in.as<uint8_t>();
   uint16_t* dsigner = (uint16_t*)(din + align_up(sig_bytes, 256));
@@ -1940,7 +918,6 @@ int mochi_rsa_public_op(mochi_ctx* c, uint32_t n, const uint8_t* sig_be, const u
          hipMemcpyAsync(z.data(), a.xbuf, sizeof(uint32_t) * z.size(), hipMemcpyDeviceToHost, st) == hipSuccess;
   }
   ok = ok && hipStreamSynchronize(st) == hipSuccess;
-  (void)hipSetDevice(save);
   if (!ok) return fail(MOCHI_EHIP, "rsa_public_op failed: %s", hipGetErrorString(hipGetLastError()));
   for (uint32_t g = 0; g < n; g++)
     for (int i = 0; i < 64; i++) {
@@ -2210,15 +1187,15 @@ mochi_signer* mochi_signer_create(int device, const char* pem) {
   }
   mochi_signer* s = new mochi_signer;
   s->device = device;
-  int save = 0;
-  (void)hipGetDevice(&save);
-  ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
-       hipEventCreateWithFlags(&s->ev_tot, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&s->order.ev, hipEventDisableTiming) == hipSuccess &&
-       hipMalloc(&s->d_key, host.size()) == hipSuccess &&
-       hipMemcpy(s->d_key, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
+  {
+    DeviceGuard dev(device);
+    ok = dev.ok && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&s->ev_tot, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&s->order.ev, hipEventDisableTiming) == hipSuccess &&
+         hipMalloc(&s->d_key, host.size()) == hipSuccess &&
+         hipMemcpy(s->d_key, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
+  }
   memset(host.data(), 0, host.size());
-  (void)hipSetDevice(save);
   if (!ok) {
     fail(MOCHI_EHIP, "signer setup failed");
     mochi_signer_destroy(s);
@@ -2241,9 +1218,7 @@ mochi_signer* mochi_signer_create(int device, const char* pem) {
 
 void mochi_signer_destroy(mochi_signer* s) {
   if (!s) return;
-  int save = 0;
-  (void)hipGetDevice(&save);
-  (void)hipSetDevice(s->device);
+  DeviceGuard dev(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->d_key) {
     (void)hipMemset(s->d_key, 0, mochi::sign_key_bytes());  // private key material
@@ -2254,7 +1229,6 @@ void mochi_signer_destroy(mochi_signer* s) {
   if (s->order.ev) (void)hipEventDestroy(s->order.ev);
   if (s->check) mochi_ctx_destroy(s->check);
   delete s;
-  (void)hipSetDevice(save);
 }
 
 }  // extern "C"
@@ -2304,13 +1278,11 @@ int mochi_signer_set_fault(mochi_signer* s, uint32_t grant_index) {
 int mochi_signer_rejected(mochi_signer* s, uint64_t* rejected) {
   if (!s || !rejected) return fail(MOCHI_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
+  DeviceGuard dev(s->device);
   uint32_t v = 0;
-  const bool ok = hipSetDevice(s->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+  const bool ok = dev.ok && hipDeviceSynchronize() == hipSuccess &&
                   hipMemcpy(&v, s->misc.p, 4, hipMemcpyDeviceToHost) == hipSuccess &&
                   hipMemset(s->misc.p, 0, 4) == hipSuccess;
-  (void)hipSetDevice(save);
   if (!ok) return fail(MOCHI_EHIP, "signer counter read failed");
   *rejected = v;
   return MOCHI_OK;
@@ -2320,9 +1292,8 @@ int mochi_sign_batch_device(mochi_signer* s, const uint8_t* grant_bytes, const u
                             const uint32_t* grant_len, uint32_t n, uint8_t* sig_out, void* stream) {
   if (!s || (n && (!grant_bytes || !grant_off || !grant_len || !sig_out))) return fail(MOCHI_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(s->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice");
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice");
   const hipError_t e = mochi::launch_rsa_sign(grant_bytes, grant_off, grant_len, n, s->d_key, sig_out, s->fault_idx,
                                               (hipStream_t)stream);
   int rc = e == hipSuccess ? MOCHI_OK : fail(MOCHI_EHIP, "k_rsa_sign: %s", hipGetErrorString(e));
@@ -2330,7 +1301,6 @@ int mochi_sign_batch_device(mochi_signer* s, const uint8_t* grant_bytes, const u
     std::lock_guard<std::mutex> ck(s->check->mu);
     rc = signer_check(s, grant_bytes, grant_off, grant_len, n, sig_out, (hipStream_t)stream);
   }
-  (void)hipSetDevice(save);
   return rc;
 }
 
@@ -2342,17 +1312,14 @@ int mochi_sign_batch(mochi_signer* s, const uint8_t* grant_bytes, uint64_t grant
       return fail(MOCHI_EINVAL, "grant %u lies outside grant_bytes", i);
   if (n == 0) return MOCHI_OK;
   std::lock_guard<std::mutex> lk(s->mu);
-  int save = 0;
-  (void)hipGetDevice(&save);
-  if (hipSetDevice(s->device) != hipSuccess) return fail(MOCHI_EHIP, "hipSetDevice");
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice");
   const size_t o_off = align_up(grant_bytes_len, 256), o_len = o_off + align_up(8 * (size_t)n, 256),
                total = o_len + align_up(4 * (size_t)n, 256), sig_bytes = (size_t)MOCHI_RSA_BYTES * n;
   int rc;
   if ((rc = s->pin_in.ensure(total)) || (rc = s->dev_in.ensure(total)) || (rc = s->pin_out.ensure(sig_bytes)) ||
-      (rc = s->dev_sig.ensure(sig_bytes))) {
-    (void)hipSetDevice(save);
+      (rc = s->dev_sig.ensure(sig_bytes)))
     return rc;
-  }
   uint8_t* pin = (uint8_t*)s->pin_in.p;
   par_memcpy(pin, grant_bytes, grant_bytes_len);
   memcpy(pin + o_off, grant_off, 8 * (size_t)n);
@@ -2372,7 +1339,6 @@ int mochi_sign_batch(mochi_signer* s, const uint8_t* grant_bytes, uint64_t grant
   if (e == hipSuccess) e = hipMemcpyAsync(s->pin_out.p, s->dev_sig.p, sig_bytes, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) memcpy(sig_out, s->pin_out.p, sig_bytes);
-  (void)hipSetDevice(save);
   return e == hipSuccess ? MOCHI_OK : fail(MOCHI_EHIP, "sign batch: %s", hipGetErrorString(e));
 }
 

@@ -4,6 +4,7 @@ Every test calls libmochi_hip through its C ABI (ctypes) and compares grant
 flags / timestamps / validity bits and certificate accept bits / reason codes /
 failing-op indices with oracle/ (OpenSSL + the restated Java verdict logic).
 """
+import ctypes
 import json
 import os
 
@@ -442,6 +443,61 @@ def test_host_pipeline_chunking(pool4, chunk):
     gs = ver.verify(_scatter_blob(s.batch, chunk), 4, True)
     assert_same(gs, o, f"scattered chunk={chunk}")
     ver.close()
+
+
+GUARD = 0x5A5AA5A5
+
+
+@pytest.mark.parametrize("chunk", [1, 0])
+def test_host_pipeline_optional_outputs_absent(pool4, chunk):
+    """mochi_verify_batch with cert_accept_bits as its only output (every other verdict
+    pointer NULL) and with all of them: the same accept bits, the oracle's, and the word
+    past the bitmap untouched -- on three chunks (32 + 32 + 6 certificates, a partial
+    last word) and in one piece."""
+    ver = mh.Verifier(pool4.moduli, 0)
+    ver.set_chunk_grants(chunk)
+    b = W.make_batch(pool4, 70, first_cert=4100).batch.normalized()
+    want = O.verify_batch(pool4.moduli, b, 4, True, 4)
+    words = (b.n_certs + 31) // 32
+    p = mh.params(4, True)
+    for only_accept in (True, False):
+        out = mh.Verdicts.alloc(b.n_grants, b.n_certs, b.n_ops)
+        out.cert_accept_bits = np.full(words + 1, GUARD, np.uint32)
+        bc, vc = b.to_c(), out.to_c()
+        if only_accept:
+            for name, _ in mh.Verdicts_C._fields_:
+                if name != "cert_accept_bits":
+                    setattr(vc, name, None)
+        rc = ver.lib.mochi_verify_batch(ver.ctx, ctypes.byref(bc), ctypes.byref(p), ctypes.byref(vc))
+        what = f"chunk={chunk} only_accept={only_accept}"
+        assert rc == mh.OK, what
+        assert out.cert_accept_bits[words] == GUARD, f"wrote past the accept bitmap ({what})"
+        out.cert_accept_bits = out.cert_accept_bits[:words].copy()
+        np.testing.assert_array_equal(out.cert_accept_bits, want.cert_accept_bits, err_msg=what)
+        if only_accept:  # nothing else was written
+            assert not out.grant_flags.any() and not out.cert_reason.any() and (out.op_decision == 0xEE).all()
+        else:
+            assert_same(out, want, what)
+    assert 0 < int(mh.unpack_bits(want.cert_accept_bits, b.n_certs).sum()) < b.n_certs
+    ver.close()
+
+
+def test_host_pipeline_empty_batch_writes_nothing(ver4):
+    """n_certs = 0 through mochi_verify_batch: MOCHI_OK, and no output array is written."""
+    b = mh.Batch(grant_bytes=np.zeros(1, np.uint8), grant_off=np.zeros(0, np.uint64), grant_len=np.zeros(0, np.uint32),
+                 sig=np.zeros((0, 256), np.uint8), signer=np.zeros(0, np.uint16), grant_key=np.zeros(0, np.uint8),
+                 cert_grant_off=np.zeros(1, np.uint32), cert_op_off=np.zeros(1, np.uint32),
+                 op_key=np.zeros(0, np.uint8), op_flags=np.zeros(0, np.uint8),
+                 expected_hash=np.zeros((0, 128), np.uint8)).normalized()
+    out = mh.Verdicts.alloc(64, 64, 64)  # room the call must not touch
+    for k in ("grant_valid_bits", "grant_flags", "grant_ts", "cert_accept_bits", "cert_reason", "cert_fail_op",
+              "op_decision", "op_g0", "op_ts"):
+        getattr(out, k).view(np.uint8)[:] = 0xA5
+    bc, vc, p = b.to_c(), out.to_c(), mh.params(4, True)
+    assert ver4.lib.mochi_verify_batch(ver4.ctx, ctypes.byref(bc), ctypes.byref(p), ctypes.byref(vc)) == mh.OK
+    for k in ("grant_valid_bits", "grant_flags", "grant_ts", "cert_accept_bits", "cert_reason", "cert_fail_op",
+              "op_decision", "op_g0", "op_ts"):
+        assert (getattr(out, k).view(np.uint8) == 0xA5).all(), k
 
 
 def test_grant_group_depth_matches_google_protobuf(pool4, ver4, golden_dir):

@@ -1,14 +1,18 @@
 """Write2ToServer wire path on the GPU (mochi_verify_write2 / mochi_write2_decode):
 the device decoder agrees with the oracle decoder array for array, with the
 golden protobuf vectors, and the wire path's verdicts equal the SoA path's."""
+import copy
+import ctypes
+
 import numpy as np
 import pytest
 
 import mochi_hip as mh
 import oracle_ffi as O
 import workload as W
+from test_w2_wire_corpus_gpu import GUARD, verify_write2_guarded
 from test_write2_wire_cpu import _golden, check_decode_against_golden
-from w2_wire_corpus import _fallback_forms, _matcher_forms, _mutate, _pack
+from w2_wire_corpus import _fallback_forms, _matcher_forms, _mutate, _pack, chunk_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +137,82 @@ def test_wire_stored_state_and_per_op_outputs(pool4k2_wire, chunk):
             np.testing.assert_array_equal(getattr(g, k), getattr(o, k), err_msg=k)
         assert {1, 2, 3, 4} <= set(np.unique(g.op_decision).tolist())
         assert {0, 9, 10} <= set(np.unique(g.cert_reason).tolist())
+    ver.close()
+
+
+def _pinned_wire(wb):
+    """A copy of the WireBatch whose arrays live in mochi_host_alloc memory, and what keeps it alive."""
+    keep = []
+
+    def pin(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(mh.PinnedHost(a.nbytes))
+        v = keep[-1].view()[:a.nbytes].view(a.dtype).reshape(a.shape)
+        v[...] = a
+        return v
+
+    p = copy.copy(wb)
+    for k in ("wire", "msg_off", "msg_len", "op_flags_off", "op_flags", "expected_hash", "op_object_ts"):
+        setattr(p, k, pin(getattr(wb, k)))
+    return p, keep
+
+
+@pytest.mark.parametrize("chunk", [1, 0])
+def test_wire_pinned_sources(pool4k2_wire, chunk):
+    """mochi_verify_write2 on arrays in pinned memory (DMA'd in place, not staged): 100 messages
+    as chunks of 32, 32, 32 and 4 -- two steady-state steps of the pipeline's two-chunk lag, its
+    drain, a partial last accept word -- and as one small chunk, which takes the one-copy
+    path and stages pinned sources anyway.  Each == the pageable result == the oracle, per-op
+    outputs and msg_status included, and no word past the accept bitmap is written."""
+    pool = pool4k2_wire
+    ver = _ver(pool)
+    ver.set_chunk_grants(chunk)
+    rng = np.random.default_rng(1234)
+    s = W.make_batch(pool, 100, first_cert=311)
+    wb = W.encode_wire_batch(s)
+    n_ops = int(wb.op_flags_off[-1])
+    wb.op_flags = rng.choice(np.array([3, 7, 7, 7, 15, 1, 2, 23, 19, 11], np.uint8), n_ops)
+    wb.op_object_ts = grant_ts_of_ops(s) + rng.integers(-2, 3, n_ops)
+    if chunk:
+        assert chunk_plan(wb.msg_len, chunk) == [(0, 32), (32, 64), (64, 96), (96, 100)]
+    pw, keep = _pinned_wire(wb)
+    ids, off = W.server_id_table(4)
+    for strict in (True, False):
+        want, want_st = O.verify_write2(pool.moduli, ids, off, wb, 4, strict)
+        for how, batch in (("pageable", wb), ("pinned", pw)):
+            g, st, guard = verify_write2_guarded(ver, batch, strict, 0)
+            what = f"{how} chunk_grants={chunk} strict={strict}"
+            assert guard == GUARD, f"wrote past the accept bitmap ({what})"
+            np.testing.assert_array_equal(st, want_st, err_msg=what)
+            for k in ("cert_accept_bits", "cert_reason", "cert_fail_op", "op_decision", "op_g0", "op_ts"):
+                np.testing.assert_array_equal(getattr(g, k), getattr(want, k), err_msg=f"{k} {what}")
+        assert len(set(want.op_decision.tolist())) >= 3 and 0 < int(want.cert_accept.sum()) < wb.n_msgs
+    del keep
+    ver.close()
+
+
+def test_wire_empty_batch_writes_nothing(pool4):
+    """n_msgs = 0 through mochi_verify_write2: MOCHI_OK, and no output array is written."""
+    ver = _ver(pool4)
+    wb = _pack([])
+    wb.op_flags_off = np.zeros(1, np.uint32)  # per-op outputs need their layout
+    wc, keep = mh.write2_batch_c(wb)
+    out = mh.Verdicts.alloc(0, 64, 64)  # room the call must not touch
+    st = np.zeros(64, np.uint8)
+    arrays = [st] + [getattr(out, k) for k in ("cert_accept_bits", "cert_reason", "cert_fail_op", "op_decision", "op_g0",
+                                               "op_ts")]
+    for a in arrays:
+        a.view(np.uint8)[:] = 0xA5
+    vc = out.to_c()
+    vc.grant_valid_bits = vc.grant_flags = vc.grant_ts = None
+    p = mh.params(4, True)
+    rc = ver.lib.mochi_verify_write2(ver.ctx, ctypes.addressof(wc), ctypes.addressof(p), ctypes.addressof(vc),
+                                     st.ctypes.data)
+    assert rc == mh.OK
+    for a in arrays:
+        assert (a.view(np.uint8) == 0xA5).all()
     ver.close()
 
 
