@@ -404,20 +404,35 @@ void resolve_timing(mochi_ctx* c) {
   (void)hipEventElapsedTime(&c->last_total_ms, e[0], e[3]);
 }
 
-int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o, hipStream_t st,
-               const uint32_t* op_out_off, const uint32_t* grant_same, const uint8_t* msg_status) {
-  const uint32_t N = b->n_grants, C = b->n_certs;
-  const uint64_t slots = mochi::slot_capacity(N, c->n_keys);
-  if (slots > 0xFFFFFFF0ull) return fail(MOCHI_EINVAL, "batch too large");
-  int rc;
-  if ((uint64_t)N + C > 0xFFFFFFF0ull) return fail(MOCHI_EINVAL, "batch too large");
-  if ((rc = ensure_scratch(c, N, C))) return rc;
-  mochi::LaunchArgs a;
-  memset(&a, 0, sizeof a);
+static_assert(mochi::kFoldLimbs == mochi::kL, "verify_layout sizes a slot of xbuf by kFoldLimbs");
+// a's batch fields for N grants of C certificates and its scratch pointers from `base`; the scratch bytes
+static size_t lay_out(mochi::LaunchArgs& a, const mochi_ctx* c, uint32_t N, uint32_t C, void* base) {
   a.n_grants = N;
   a.n_certs = C;
   a.n_keys = c->n_keys;
-  a.n_slots = (uint32_t)slots;
+  a.n_slots = (uint32_t)mochi::slot_capacity(N, c->n_keys);
+  return mochi::verify_layout(a, base);
+}
+// the scratch bytes of N grants of C certificates; 0: the batch is too large
+static size_t verify_bytes(const mochi_ctx* c, uint32_t N, uint32_t C) {
+  if (mochi::slot_capacity(N, c->n_keys) > 0xFFFFFFF0ull || (uint64_t)N + C > 0xFFFFFFF0ull) return 0;
+  mochi::LaunchArgs a;
+  return lay_out(a, c, N, C, nullptr);
+}
+// The one place that grows the verify scratch.
+int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C) {
+  const size_t bytes = verify_bytes(c, N, C);
+  return bytes ? c->scratch.ensure(bytes) : fail(MOCHI_EINVAL, "batch too large");
+}
+
+int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o, hipStream_t st,
+               const uint32_t* op_out_off, const uint32_t* grant_same, const uint8_t* msg_status) {
+  const uint32_t N = b->n_grants, C = b->n_certs;
+  int rc;
+  if ((rc = ensure_scratch(c, N, C))) return rc;
+  mochi::LaunchArgs a;
+  memset(&a, 0, sizeof a);
+  lay_out(a, c, N, C, c->scratch.p);
   a.blob = b->grant_bytes;
   a.grant_off = b->grant_off;
   a.grant_len = b->grant_len;
@@ -440,19 +455,8 @@ int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_
   a.strict_gt = p->strict_gt ? 1 : 0;
   a.keys = c->d_keys;
   a.fold = c->d_fold;
-  a.digest = c->digest.as<uint32_t>();  // distinct prep results: N + C entries (kernels.h)
-  a.n_dist = N + C;
-  a.lead = c->lead.as<uint32_t>();
-  a.ts = o->grant_ts ? o->grant_ts : c->ts.as<int64_t>();
-  a.hash_off = c->hash_off.as<uint64_t>();
-  a.hash_len = c->hash_len.as<uint32_t>();
-  a.flags = o->grant_flags ? o->grant_flags : c->flags.as<uint8_t>();
-  a.count = c->count.as<uint32_t>();
-  a.cursor = c->cursor.as<uint32_t>();
-  a.total = c->total.as<uint32_t>();
-  a.perm = c->perm.as<uint32_t>();
-  a.xbuf = c->xbuf.as<uint32_t>();
-  a.rare = c->dedup.as<uint8_t>();
+  if (o->grant_ts) a.ts = o->grant_ts;
+  if (o->grant_flags) a.flags = o->grant_flags;
   a.small_grants = c->small_grants;
   a.grant_same = grant_same;
   a.grant_valid_bits = o->grant_valid_bits;
@@ -479,35 +483,15 @@ int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_
   return MOCHI_OK;
 }
 
-// Verify scratch for N grants of C certificates: per grant (ts, flags, rare,
-// lead), per distinct prep result (N + C: digest, hash slice), per slot (perm, z).
-int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C) {
-  const uint64_t slots = mochi::slot_capacity(N, c->n_keys);
-  const size_t ND = (size_t)N + C;
-  int rc;
-  if ((rc = c->digest.ensure(sizeof(uint32_t) * 8 * ND)) || (rc = c->dedup.ensure((size_t)N)) ||
-      (rc = c->ts.ensure(sizeof(int64_t) * (size_t)N)) || (rc = c->hash_off.ensure(sizeof(uint64_t) * ND)) ||
-      (rc = c->hash_len.ensure(sizeof(uint32_t) * ND)) || (rc = c->flags.ensure((size_t)N)) ||
-      (rc = c->lead.ensure(sizeof(uint32_t) * (size_t)N)) ||
-      (rc = c->count.ensure(sizeof(uint32_t) * c->n_keys)) || (rc = c->cursor.ensure(sizeof(uint32_t) * c->n_keys)) ||
-      (rc = c->total.ensure(mochi::kTotalWords * sizeof(uint32_t))) || (rc = c->perm.ensure(sizeof(uint32_t) * (size_t)slots)) ||
-      (rc = c->xbuf.ensure(sizeof(uint32_t) * mochi::kL * (size_t)slots)))
-    return rc;
-  return MOCHI_OK;
-}
-
 // ---- Write2ToServer wire path -------------------------------------------------
 // Decode on the device (w2_decode.hip), then the ordinary verify path over the
 // decoded batch, then the per-message status fix-up.  All pointers device.
 // Decode, phase 1 (w2_decode.hip): validate + count + CSR scans for the M
-// messages of `w`.  cnt: mochi::w2_scratch_words(M) device words (counts, CSR
-// offsets and the level-by-level decode state of this batch, so a pipelined
-// caller can count chunk j+1 while chunk j verifies);
+// messages of `w`.  cnt: this batch's w2_count_layout bytes on the device;
 // the totals (N, O, n_mgs) land in tot_host (pinned) once ev_tot completes.
-int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, uint32_t* cnt, uint32_t* tot_host,
+int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, void* cnt, uint32_t* tot_host,
              hipEvent_t ev_tot, hipStream_t st, mochi::W2Args* a) {
   const uint32_t M = w->n_msgs;
-  const size_t m1 = (size_t)M + 1;
   size_t scan_bytes = 0;  // a small batch needs none (and the size query is ~7 host API calls)
   if (!mochi::w2_small(M)) HIP_TRY(mochi::w2_scan_temp_bytes(M + 1, &scan_bytes));
   if (scan_bytes > c->w2_scan.cap) {
@@ -526,19 +510,7 @@ int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, uint32_
   a->ids = c->ids.as<uint8_t>();
   a->id_off = c->id_off.as<uint32_t>();
   a->n_ids = c->n_ids;
-  a->cnt_g = cnt;
-  a->cnt_o = cnt + m1;
-  a->cnt_m = cnt + 2 * m1;
-  a->cert_grant_off = cnt + 3 * m1;
-  a->cert_op_off = cnt + 4 * m1;
-  a->cert_mg_off = cnt + 5 * m1;
-  a->cnt_ce = cnt + 6 * m1;
-  a->ce = cnt + (size_t)mochi::kW2MsgArrays * m1;
-  a->ce_cap = mochi::kW2MaxCertEntries * (uint32_t)m1;
-  a->inl = (uint32_t*)(((uintptr_t)(a->ce + mochi::kW2CeArrays * (size_t)a->ce_cap) + 15) & ~(uintptr_t)15);
-  a->inl_ops = a->inl + 4 * (size_t)mochi::kW2InlEntries * m1;
-  a->cnt4 = a->inl_ops + 2 * (size_t)mochi::kW2InlOps * m1;  // 16-byte aligned: the two above are multiples of 4 words
-  a->off4 = a->cnt4 + 4 * m1;
+  mochi::w2_count_layout(*a, cnt);
   a->status = status;
   a->scan_temp = c->w2_scan.p;
   a->scan_temp_bytes = c->w2_scan.cap;
@@ -549,49 +521,20 @@ int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, uint32_
   return MOCHI_OK;
 }
 
-// Grow a decode buffer; if it must be reallocated, first let the stream drain
-// (an earlier chunk's kernels may still read the old allocation).
-static int grow(DevBuf& b, size_t bytes, hipStream_t st) {
-  if (bytes <= b.cap) return MOCHI_OK;
-  HIP_TRY(hipStreamSynchronize(st));
-  return b.ensure(bytes);
-}
-
 // Decode, phase 2: emit the SoA batch (N grants, O ops, NM MultiGrants from
 // phase 1), then the verify path and the per-message status fix-up.  Per-op
 // outputs follow the caller's op_flags_off layout (`op_out_off`, device).
 int w2_verify(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
               mochi::W2Args& a, uint32_t N, uint32_t O, uint32_t NM, const uint32_t* op_out_off, hipStream_t st,
               bool decode_only) {
-  int rc;
-  if ((rc = grow(c->w2_goff, 8 * (size_t)N, st)) || (rc = grow(c->w2_glen, 4 * (size_t)N, st)) ||
-      (rc = grow(c->w2_sig, (size_t)MOCHI_RSA_BYTES * N, st)) || (rc = grow(c->w2_signer, 2 * (size_t)N, st)) ||
-      (rc = grow(c->w2_gkey, N, st)) || (rc = grow(c->w2_okey, O, st)) || (rc = grow(c->w2_oflags, O, st)) ||
-      (rc = grow(c->w2_sigsrc, 8 * (size_t)N, st)) || (rc = grow(c->w2_mgo, 4 * ((size_t)NM + 1), st)) ||
-      (rc = grow(c->w2_ots, 8 * (size_t)O, st)) || (rc = grow(c->w2_okoff, 8 * (size_t)O, st)) ||
-      (rc = grow(c->w2_oklen, 4 * (size_t)O, st)) || (rc = grow(c->w2_same, 4 * (size_t)N, st)))
-    return rc;
-  if (!decode_only) {  // the verify scratch grows only once the stream has drained
-    const uint64_t slots = mochi::slot_capacity(N, c->n_keys);
-    if (sizeof(uint32_t) * mochi::kL * slots > c->xbuf.cap || sizeof(uint32_t) * 8 * ((size_t)N + a.M) > c->digest.cap ||
-        sizeof(uint32_t) * (size_t)N > c->lead.cap)
-      HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = ensure_scratch(c, N, a.M))) return rc;
-  }
   a.N = N;
-  a.sig_src = c->w2_sigsrc.as<uint64_t>();
-  a.grant_off = c->w2_goff.as<uint64_t>();
-  a.grant_len = c->w2_glen.as<uint32_t>();
-  a.sig = c->w2_sig.as<uint8_t>();
-  a.signer = c->w2_signer.as<uint16_t>();
-  a.grant_key = c->w2_gkey.as<uint8_t>();
-  a.op_key = c->w2_okey.as<uint8_t>();
-  a.op_flags = c->w2_oflags.as<uint8_t>();
-  a.op_object_ts = c->w2_ots.as<int64_t>();
-  a.op_key_off = c->w2_okoff.as<uint64_t>();
-  a.op_key_len = c->w2_oklen.as<uint32_t>();
-  a.mg_grant_off = c->w2_mgo.as<uint32_t>();
-  a.grant_same = c->w2_same.as<uint32_t>();
+  const size_t out_bytes = mochi::w2_emit_layout(a, O, NM, nullptr);
+  const size_t ver_bytes = decode_only ? 0 : verify_bytes(c, N, a.M);  // 0 too where ensure_scratch refuses the batch
+  // a buffer that must be reallocated: first let the stream drain (an earlier chunk's kernels may still use it)
+  if (out_bytes > c->w2_out.cap || ver_bytes > c->scratch.cap) HIP_TRY(hipStreamSynchronize(st));
+  int rc;
+  if ((rc = c->w2_out.ensure(out_bytes)) || (!decode_only && (rc = ensure_scratch(c, N, a.M)))) return rc;
+  mochi::w2_emit_layout(a, O, NM, c->w2_out.p);
   HIP_TRY(mochi::launch_w2_emit(a, st));
   if (decode_only) return MOCHI_OK;
   mochi_batch db;
@@ -641,13 +584,14 @@ static int run_write2_device(mochi_ctx* c, const mochi_write2_batch* w, const mo
   const uint32_t M = w->n_msgs;
   if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
   int rc;
-  if ((rc = c->w2_cnt.ensure(4 * mochi::w2_scratch_words(M))) || (rc = c->w2_tot.ensure(16)) ||
+  mochi::W2Args a;
+  a.M = M;
+  if ((rc = c->w2_cnt.ensure(mochi::w2_count_layout(a, nullptr))) || (rc = c->w2_tot.ensure(16)) ||
       (!status && (rc = c->w2_status.ensure(M ? M : 1))))
     return rc;
   HIP_TRY(scratch_acquire(c, st));
-  mochi::W2Args a;
   uint32_t* tot = (uint32_t*)c->w2_tot.p;
-  if ((rc = w2_count(c, w, status ? status : c->w2_status.as<uint8_t>(), c->w2_cnt.as<uint32_t>(), tot, c->ev_tot, st, &a)))
+  if ((rc = w2_count(c, w, status ? status : c->w2_status.as<uint8_t>(), c->w2_cnt.p, tot, c->ev_tot, st, &a)))
     return rc;
   HIP_TRY(hipEventSynchronize(c->ev_tot));
   if ((rc = w2_verify(c, w, p, o, a, tot[0], tot[1], tot[2], w->op_flags_off, st, false))) return rc;
@@ -871,34 +815,22 @@ int mochi_rsa_public_op(mochi_ctx* c, uint32_t n, const uint8_t* sig_be, const u
   new_call(c);
   DeviceGuard dev(c->device);
   if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
-  const uint64_t slots = mochi::slot_capacity(n, c->n_keys);
   const size_t sig_bytes = (size_t)MOCHI_RSA_BYTES * n, y_bytes = sizeof(uint32_t) * 64 * (size_t)n;
   int rc;
   if ((rc = c->dev_in.ensure(align_up(sig_bytes, 256) + sizeof(uint16_t) * n)) || (rc = c->dev_out.ensure(y_bytes)) ||
-      (rc = c->digest.ensure(sizeof(uint32_t) * 8 * (size_t)n)) || (rc = c->flags.ensure(n)) ||
-      (rc = c->count.ensure(sizeof(uint32_t) * c->n_keys)) || (rc = c->cursor.ensure(sizeof(uint32_t) * c->n_keys)) ||
-      (rc = c->total.ensure(mochi::kTotalWords * sizeof(uint32_t))) || (rc = c->perm.ensure(sizeof(uint32_t) * (size_t)slots)) ||
-      (rc = c->xbuf.ensure(sizeof(uint32_t) * mochi::kL * (size_t)slots)))
+      (rc = ensure_scratch(c, n, 0)))
     return rc;
   hipStream_t st = c->stream;
   uint8_t* din = c->dev_in.as<uint8_t>();
   uint16_t* dsigner = (uint16_t*)(din + align_up(sig_bytes, 256));
   mochi::LaunchArgs a;
   memset(&a, 0, sizeof a);
-  a.n_grants = n;
-  a.n_keys = c->n_keys;
-  a.n_slots = (uint32_t)slots;
+  lay_out(a, c, n, 0, c->scratch.p);
+  const uint64_t slots = a.n_slots;
   a.sig = din;
   a.signer = dsigner;
   a.keys = c->d_keys;
   a.fold = c->d_fold;
-  a.digest = c->digest.as<uint32_t>();
-  a.flags = c->flags.as<uint8_t>();
-  a.count = c->count.as<uint32_t>();
-  a.cursor = c->cursor.as<uint32_t>();
-  a.total = c->total.as<uint32_t>();
-  a.perm = c->perm.as<uint32_t>();
-  a.xbuf = c->xbuf.as<uint32_t>();
   a.dbg_y = c->dev_out.as<uint32_t>();
   a.skip_prep_tally = true;
   // the context's small-batch setting picks the launch sequence as in the verify

@@ -172,15 +172,14 @@ struct mochi_ctx {
   mochi::KeyEntry* d_keys = nullptr;
   mochi::FoldKey* d_fold = nullptr;  // per-key k_rsa_pow fold matrices (~101 KB each)
   std::mutex mu;
-  // verify scratch
-  mochi::DevBuf digest, ts, hash_off, hash_len, flags, count, cursor, total, perm, xbuf, dedup, lead;
+  mochi::DevBuf scratch;  // verify scratch (verify_layout, kernels.h)
   // host-path device copies
   mochi::DevBuf dev_in, dev_out;
   mochi::PinnedBuf pin_in, pin_out;
   hipStream_t s_in = nullptr, s_out = nullptr;  // host-path copy streams
   hipStream_t aux = nullptr;                     // grant prep (high priority), beside k_rsa_pow
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  mochi::ScratchOrder order;  // over digest / perm / xbuf / the decode and encode buffers
+  mochi::ScratchOrder order;  // over scratch and the decode and encode buffers
   std::vector<hipEvent_t> chunk_ev;              // host-path chunk hand-offs
   std::vector<hipEvent_t> tot_ev;                // wire host path: per-chunk decode totals on the host
   // two sets of the host-path call's span events: a call records into one while
@@ -197,8 +196,7 @@ struct mochi_ctx {
   mochi::DevBuf ids, id_off;
   uint32_t n_ids = 0;
   std::vector<std::string> server_ids;  // host copy for the fallback decoder (w2_host.cpp)
-  mochi::DevBuf w2_cnt, w2_status, w2_scan, w2_goff, w2_glen, w2_sig, w2_signer, w2_gkey, w2_okey, w2_oflags, w2_sigsrc,
-      w2_mgo, w2_ots, w2_okoff, w2_oklen, w2_same;
+  mochi::DevBuf w2_cnt, w2_status, w2_scan, w2_out;  // w2_cnt: w2_count_layout per chunk; w2_out: w2_emit_layout
   mochi::PinnedBuf w2_tot;
   hipEvent_t ev_tot = nullptr;
   mochi::EncState w2e;  // Write2 encoder (w2_encode.hip); its total is the wire size
@@ -229,7 +227,7 @@ int ensure_scratch(mochi_ctx* c, uint32_t N, uint32_t C);
 int run_device(mochi_ctx* c, const mochi_batch* b, const mochi_params* p, mochi_verdicts* o, hipStream_t st,
                const uint32_t* op_out_off = nullptr, const uint32_t* grant_same = nullptr,
                const uint8_t* msg_status = nullptr);
-int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, uint32_t* cnt, uint32_t* tot_host,
+int w2_count(mochi_ctx* c, const mochi_write2_batch* w, uint8_t* status, void* cnt, uint32_t* tot_host,
              hipEvent_t ev_tot, hipStream_t st, W2Args* a);
 int w2_verify(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o, W2Args& a,
               uint32_t N, uint32_t O, uint32_t NM, const uint32_t* op_out_off, hipStream_t st, bool decode_only);

@@ -1,39 +1,17 @@
 // enc_launch.h — host-side launch helpers shared by the wire encoders
 // (w2_encode.hip, w1_issue.hip, w1_reply.hip): grid arithmetic, the scratch
-// layout cursor, the per-kernel profiling stamps and the 64-bit hipcub scans.
+// layout cursor (carve.h), the per-kernel profiling stamps and the 64-bit hipcub scans.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "carve.h"
+
 namespace mochi {
 
 inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// Cursor over one call's scratch.  Each encoder has ONE layout function that
-// takes its arrays from a Carve in order: run on a null base it only counts
-// (bytes() is what to allocate), run on the allocation it hands out the same
-// arrays, so the size and the pointers cannot disagree.  Every array starts on
-// a 16-byte boundary; arrays taken one after the other are adjacent up to that
-// rounding.
-class Carve {
- public:
-  explicit Carve(void* base) : base_(base ? (uint8_t*)(((uintptr_t)base + 15) & ~(uintptr_t)15) : nullptr) {}
-  template <class T>
-  T* take(size_t count) {
-    const size_t at = used_;
-    used_ += up16(count * sizeof(T));
-    return base_ ? (T*)(base_ + at) : nullptr;
-  }
-  // the arrays taken so far, plus the 16 bytes that aligning the base may skip
-  size_t bytes() const { return used_ + 16; }
-
- private:
-  uint8_t* base_;
-  size_t used_ = 0;
-};
 
 // per-kernel timing: records event i on the stream when the call is profiled (ev != null)
 struct Stamps {

@@ -551,7 +551,7 @@ static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const m
   struct Chunk {
     uint32_t m0, m1;
     ByteRange wire;
-    size_t cnt;  // its decode scratch, words into w2_cnt
+    size_t cnt;  // its decode scratch, bytes into w2_cnt
     SegIn seg[kNumW2Seg];
     mochi_write2_batch dw;  // the chunk on the device
     mochi::W2Args args;
@@ -565,7 +565,8 @@ static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const m
     ch.push_back({m0, m1, {}, cnt_total, {}, {}, {}});
     Chunk& k = ch.back();
     k.wire.add(w->msg_off, w->msg_len, m0, m1);
-    cnt_total += mochi::w2_scratch_words(m1 - m0);
+    k.args.M = m1 - m0;
+    cnt_total += mochi::w2_count_layout(k.args, nullptr);
     const size_t nm = m1 - m0, no = ofo ? ofo[m1] - ofo[m0] : 0;
     const bool ots = ofo && w->op_object_ts;
     SegIn* s = k.seg;
@@ -579,7 +580,7 @@ static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const m
     for (SegIn& x : k.seg) x.off = hp.in.take(x.bytes);
   });
   const size_t nch = ch.size();
-  if ((rc = c->w2_cnt.ensure(4 * cnt_total)) || (rc = c->w2_tot.ensure(16 * nch)) ||
+  if ((rc = c->w2_cnt.ensure(cnt_total)) || (rc = c->w2_tot.ensure(16 * nch)) ||
       (rc = ensure_events(c->tot_ev, nch)))
     return rc;
   uint32_t* tot = (uint32_t*)c->w2_tot.p;
@@ -631,7 +632,7 @@ static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const m
     dw.op_flags = ofo ? hp.dev(s[kW2OpFlags]) : nullptr;
     dw.op_object_ts = s[kW2OpObjTs].bytes ? (const int64_t*)hp.dev(s[kW2OpObjTs]) : nullptr;
     dw.expected_hash = hp.dev(s[kW2ExpHash]);
-    if ((rc = w2_count(c, &dw, (uint8_t*)hp.dev_out(kW2Status) + k.m0, c->w2_cnt.as<uint32_t>() + k.cnt, tot + 4 * j,
+    if ((rc = w2_count(c, &dw, (uint8_t*)hp.dev_out(kW2Status) + k.m0, c->w2_cnt.as<uint8_t>() + k.cnt, tot + 4 * j,
                        c->tot_ev[j], st, &k.args)))
       return rc;
     // the verify of chunk j - kW2Lag: its totals are read on the host, so the

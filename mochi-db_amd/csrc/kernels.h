@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "carve.h"
 #include "fold.h"
 
 namespace mochi {
@@ -82,6 +83,27 @@ enum ProfStage { kStagePrep = 0, kStageBucket, kStagePow, kStageFinal, kStageTal
 // (one k_rsa_pow block of one signer).
 inline uint64_t slot_capacity(uint32_t n_grants, uint32_t n_keys) {
   return (uint64_t)n_grants + (uint64_t)kBucketAlign * (n_keys < n_grants ? n_keys : n_grants);
+}
+
+// The verify scratch of a's batch fields (n_grants, n_certs, n_keys, n_slots) in one allocation; returns
+// its bytes (Carve: a null base only counts).  Every array: 256-byte aligned, whole 256-byte units.
+inline size_t verify_layout(LaunchArgs& a, void* base) {
+  const size_t N = a.n_grants, ND = N + a.n_certs;
+  Carve c(base, 256);
+  a.n_dist = (uint32_t)ND;
+  a.digest = c.take<uint32_t>(8 * ND);
+  a.rare = c.take<uint8_t>(N);
+  a.ts = c.take<int64_t>(N);
+  a.hash_off = c.take<uint64_t>(ND);
+  a.hash_len = c.take<uint32_t>(ND);
+  a.flags = c.take<uint8_t>(N);
+  a.lead = c.take<uint32_t>(N);
+  a.count = c.take<uint32_t>(a.n_keys);
+  a.cursor = c.take<uint32_t>(a.n_keys);
+  a.total = c.take<uint32_t>(kTotalWords);
+  a.perm = c.take<uint32_t>(a.n_slots);
+  a.xbuf = c.take<uint32_t>((size_t)kFoldLimbs * a.n_slots);  // kFoldLimbs == kL limbs a slot
+  return c.bytes();
 }
 
 hipError_t launch_verify(const LaunchArgs& a, hipStream_t stream);

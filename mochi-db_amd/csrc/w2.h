@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "carve.h"
+
 namespace mochi {
 
 // Write2ToServer wire decode (w2_decode.hip).  Device pointers.
@@ -55,12 +57,9 @@ struct W2Args {
   uint32_t* mg_grant_off;    // [n_mgs+1]
   uint32_t* grant_same;      // [N] or null: an earlier grant of the message with the same bytes (k_w2_mg's match)
 };
-// Device words of one decode's per-batch scratch: 13 arrays of M+1 (counts,
-// CSR offsets, level-1 state) + the certificate-entry list (at most
-// kW2MaxCertEntries per message on the fast path, kW2CeArrays words each) +
-// level 1's entry records + the packed per-message counts and their scan.
+// The certificate-entry list: at most kW2MaxCertEntries per message on the fast
+// path, kW2CeArrays words each.
 constexpr uint32_t kW2MaxCertEntries = 32;
-constexpr int kW2MsgArrays = 13;
 constexpr int kW2CeArrays = 11;
 // Level 1 records the key / value slices of a message's first kW2InlEntries
 // certificate entries, so the compact entry list is copied, not re-parsed.
@@ -68,10 +67,45 @@ constexpr uint32_t kW2InlEntries = 4;
 // ... and the operand1 (key) slices of its first kW2InlOps operations, so level
 // 2's key-slot lookup compares keys instead of re-walking the transaction.
 constexpr uint32_t kW2InlOps = 4;
-inline size_t w2_scratch_words(uint32_t M) {
-  return (size_t)kW2MsgArrays * ((size_t)M + 1) + kW2CeArrays * (size_t)kW2MaxCertEntries * ((size_t)M + 1) +
-         4 * (size_t)kW2InlEntries * ((size_t)M + 1) + 2 * (size_t)kW2InlOps * ((size_t)M + 1) + 8 * ((size_t)M + 1) +
-         4;  // + 4: 16-byte alignment
+// The decode scratch's two layout functions; each returns the bytes to allocate (Carve: a null
+// base only counts).  Every array: 256-byte aligned, whole 256-byte units.
+// Phase 1, from a.M: the counts, CSR offsets and level-by-level decode state of one batch.
+inline size_t w2_count_layout(W2Args& a, void* base) {
+  const size_t m1 = (size_t)a.M + 1;
+  Carve c(base, 256);
+  a.cnt_g = c.take<uint32_t>(m1);
+  a.cnt_o = c.take<uint32_t>(m1);
+  a.cnt_m = c.take<uint32_t>(m1);
+  a.cert_grant_off = c.take<uint32_t>(m1);
+  a.cert_op_off = c.take<uint32_t>(m1);
+  a.cert_mg_off = c.take<uint32_t>(m1);
+  a.cnt_ce = c.take<uint32_t>(7 * m1);  // one run: msg_view (w2_decode.hip) splits it at stride m1
+  a.ce_cap = kW2MaxCertEntries * (uint32_t)m1;
+  a.ce = c.take<uint32_t>(kW2CeArrays * (size_t)a.ce_cap);  // one run: ce_view splits it at stride ce_cap
+  a.inl = c.take<uint32_t>(4 * (size_t)kW2InlEntries * m1);
+  a.inl_ops = c.take<uint32_t>(2 * (size_t)kW2InlOps * m1);
+  a.cnt4 = c.take<uint32_t>(4 * m1);
+  a.off4 = c.take<uint32_t>(4 * m1);
+  return c.bytes();
+}
+// Phase 2, from a.N and phase 1's totals (O operations, NM MultiGrants): the emitted SoA batch.
+inline size_t w2_emit_layout(W2Args& a, uint32_t O, uint32_t NM, void* base) {
+  const size_t N = a.N;
+  Carve c(base, 256);
+  a.grant_off = c.take<uint64_t>(N);
+  a.grant_len = c.take<uint32_t>(N);
+  a.sig = c.take<uint8_t>(256 * N);  // MOCHI_RSA_BYTES each
+  a.signer = c.take<uint16_t>(N);
+  a.grant_key = c.take<uint8_t>(N);
+  a.op_key = c.take<uint8_t>(O);
+  a.op_flags = c.take<uint8_t>(O);
+  a.sig_src = c.take<uint64_t>(N);
+  a.mg_grant_off = c.take<uint32_t>((size_t)NM + 1);
+  a.op_object_ts = c.take<int64_t>(O);
+  a.op_key_off = c.take<uint64_t>(O);
+  a.op_key_len = c.take<uint32_t>(O);
+  a.grant_same = c.take<uint32_t>(N);
+  return c.bytes();
 }
 hipError_t w2_scan_temp_bytes(uint32_t n, size_t* bytes);
 // M messages decode without the hipcub scans (single-block kernels; no scan scratch)

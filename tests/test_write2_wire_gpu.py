@@ -562,6 +562,65 @@ def test_wire_layout_matcher_edges(pool4):
     ver.close()
 
 
+def test_scratch_regrowth_sequence(pool4):
+    """One context through batches of 3 -> 1100 -> 40 -> 1500 -> 3 certificates, every entry point
+    at each size: the verify scratch, the decode scratch and the emitted batch each grow twice
+    and are then reused by smaller batches laid out differently inside them.  1100 messages
+    cross the decoder's small-batch bound (1024) and their grants the verifier's (4096); the
+    host paths run 64-grant chunks, so the wire call keeps chunks in flight while buffers grow.
+    Verdicts, statuses, per-op outputs and decode arrays == the oracle's, s^65537 == Python's."""
+    import torch
+
+    ver = _ver(pool4)
+    ids, off = W.server_id_table(4)
+    stream = torch.cuda.current_stream().cuda_stream
+    certs = ("cert_accept_bits", "cert_reason", "cert_fail_op", "op_decision", "op_g0", "op_ts")
+    grants = ("grant_flags", "grant_ts", "grant_valid_bits")
+    pows = {}
+    for n, first in ((3, 7), (1100, 100), (40, 2000), (1500, 3000), (3, 9000)):
+        s = W.make_batch(pool4, n, first_cert=first)
+        wb = W.encode_wire_batch(s)
+        want = O.verify_batch(pool4.moduli, s.batch, 4, True)
+        want_w, want_st = O.verify_write2(pool4.moduli, ids, off, wb, 4, True)
+        want_d = O.w2_decode(wb, ids, off)
+        assert (want_st == 0).all()  # no host fallback: the device entry decides every message too
+        ver.set_chunk_grants(64)
+        g = ver.verify(s.batch, 4, True)
+        for k in certs + grants:
+            np.testing.assert_array_equal(getattr(g, k), getattr(want, k), err_msg=f"verify {k} n={n}")
+        g, st = ver.verify_write2(wb, 4, True)
+        np.testing.assert_array_equal(st, want_st, err_msg=f"verify_write2 status n={n}")
+        for k in certs:
+            np.testing.assert_array_equal(getattr(g, k), getattr(want_w, k), err_msg=f"verify_write2 {k} n={n}")
+        assert_decode_equal(ver.decode_write2(wb), want_d, f"n={n}")
+        ver.set_chunk_grants(0)
+        dev = mh.DeviceBatch(s.batch, 0)
+        out = mh.DeviceVerdicts(dev.n_grants, dev.n_certs, 0, full=True, n_ops=dev.n_ops)
+        ver.verify_device(dev, out, 4, True, stream=stream)
+        dwb = mh.DeviceWireBatch(wb, 0)
+        out_w = mh.DeviceVerdicts(0, n, 0, full=True, n_ops=int(wb.op_flags_off[-1]))
+        ver.verify_write2_device(dwb, out_w, 4, True, stream=stream)
+        torch.cuda.synchronize()
+        h, h_w = out.to_host(), out_w.to_host()
+        for k in certs + grants:
+            np.testing.assert_array_equal(getattr(h, k), getattr(want, k), err_msg=f"verify_device {k} n={n}")
+        np.testing.assert_array_equal(dwb.status.cpu().numpy()[:n], want_st, err_msg=f"device status n={n}")
+        for k in certs:
+            np.testing.assert_array_equal(getattr(h_w, k), getattr(want_w, k), err_msg=f"verify_write2_device {k} n={n}")
+        b = s.batch
+        y = mh.rsa_public_op(ver, b.sig, b.signer)
+        for i in range(b.n_grants):
+            key = (b.sig[i].tobytes(), int(b.signer[i]))
+            if key not in pows:  # the pool's signatures repeat
+                mod = int.from_bytes(pool4.moduli[key[1]], "big")
+                sig = int.from_bytes(key[0], "big")
+                pows[key] = pow(sig, 65537, mod) if sig < mod else None  # a flipped top bit: outside the operation's domain
+            if pows[key] is not None:
+                assert int.from_bytes(y[i].tobytes(), "big") == pows[key], f"rsa_public_op grant {i} n={n}"
+    assert sum(v is not None for v in pows.values()) > len(pows) // 2
+    ver.close()
+
+
 def test_context_closed_before_its_batcher(pool4):
     """Closing a Verifier while a Batcher on it is alive (explicit close, or __del__
     order in a host language) neither blocks nor frees the context under the
