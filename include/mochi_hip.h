@@ -842,6 +842,150 @@ int mochi_write1_reply_encode_device(mochi_signer* s, const mochi_write1_batch* 
 int mochi_signer_read_reply_profile(mochi_signer* s, float* kernel_ms, uint32_t n);
 
 /* ------------------------------------------------------------------------
+ * Write1 REPLY DECODE: the client's side of the bodies above.  The
+ * Write1OkFromServer / Write1RefusedFromServer bytes a client received become
+ * the arrays mochi_write1_classify and mochi_write2_source read, with
+ * protobuf-java 3.16.3 parsing semantics (as the Write2 decoder: singular
+ * fields last-wins, unknown fields and groups to depth 100 skipped, strings
+ * and map keys strict UTF-8, maps in LinkedHashMap order -- a repeated key
+ * keeps its first position and takes its last value --, every Grant and
+ * WriteCertificate value parsed all the way down even where a later entry
+ * replaces it).  The bytes are a Byzantine server's: every read stays inside
+ * the response's slice (the signature gather reads the 16-byte-aligned chunks
+ * that hold a signature byte, as the Write2 decoder's does).
+ *
+ * Input.  Response p is wire[resp_off[p], +resp_len[p]) (field 108 / 109 of a
+ * ProtocolMessage; any alignment; slices may alias) with payload case
+ * resp_kind[p] (MOCHI_W1_*), known from the envelope.  Request q owns
+ * responses [req_resp_off[q], req_resp_off[q+1]) in arrival order (a CSR over
+ * all n_resps) and sent the ops [req_op_off[q], req_op_off[q+1]) (at most
+ * MOCHI_MAX_OPS_PER_CERT), op o with operand1 strings[op_key_off[o],
+ * +op_key_len[o]).  n_resps is at most 2^24.
+ * ------------------------------------------------------------------------ */
+typedef struct mochi_write1_replies {
+  uint32_t n_resps, n_reqs, n_ops, _pad0;      /* P, Q, O */
+  const uint8_t*  wire;    uint64_t wire_len;
+  const uint64_t* resp_off;      /* [P] */
+  const uint32_t* resp_len;      /* [P] */
+  const uint8_t*  resp_kind;     /* [P] MOCHI_W1_* */
+  const uint32_t* req_resp_off;  /* [Q+1] */
+  const uint8_t*  strings; uint64_t strings_len;
+  const uint32_t* req_op_off;    /* [Q+1] */
+  const uint64_t* op_key_off;    /* [O] */
+  const uint32_t* op_key_len;    /* [O] */
+} mochi_write1_replies;
+
+/* Per-response decode status. */
+enum mochi_w1r_status {
+  MOCHI_W1R_OK = 0,
+  /* protobuf-java would throw while parsing the body as its message type */
+  MOCHI_W1R_MALFORMED = 1,
+  /* well-formed (validated whole, never malformed) but outside the shape this
+   * decoder handles, not decoded: multiGrant given more than once (a merge); a
+   * grants or currentCertificates entry carrying its value more than once; a
+   * decoded Grant whose bytes are not what Grant.toByteArray() would write;
+   * more than 64 grants, grantSignatures or currentCertificates entries on the
+   * wire (repeated keys included) */
+  MOCHI_W1R_FALLBACK = 2,
+  /* decoded like an OK one, but MultiGrant.serverId equals no table entry */
+  MOCHI_W1R_UNKNOWN_SERVER = 3,
+};
+#define MOCHI_W1G_HAS_SIG 0x01     /* grantSignatures[map key] exists with exactly 256 bytes */
+#define MOCHI_W1G_KEY_DIFFERS 0x02 /* the map key is not Grant.objectId                      */
+
+/* Output; every array is the caller's.  Responses of kind REQUEST_FAILED /
+ * OTHER are not parsed: status OK, no grants, no certificates.  A response
+ * whose status is MALFORMED or FALLBACK has resp_kind_out MOCHI_W1_OTHER (so
+ * that a reply nobody decoded never counts as an empty OK), no grants and no
+ * certificates.  A missing multiGrant (an empty body too) is the default
+ * MultiGrant: no grants, serverId empty.
+ *   resp_server: the key index of MultiGrant.serverId.  Where no table entry
+ *     equals it, and for every response that was not decoded, it is
+ *     0x80000000 | p: distinct from every key index and from every other
+ *     response's value, so such a reply never supersedes another server's in
+ *     mochi_write1_classify.
+ *   mg_signer: the same index as mochi_write2_source.mg_signer takes it,
+ *     0xFFFF if unknown or not decoded.
+ *   resp_client_off / _len: MultiGrant.clientId (last occurrence), an offset
+ *     into `wire`; 0 / 0 if not decoded.  Here and below, a field that is
+ *     absent gives the response's own offset and length 0.
+ *   resp_grant_off / resp_cert_off [P+1]: CSRs over the grants / certificates.
+ * Per grant, in map order: grant_off / grant_len point into `wire` (zero
+ * copy); grant_key = slot of the first op of the response's request whose
+ * operand1 byte-equals the MAP KEY (what allGrants.get(op.getOperand1()) finds,
+ * MochiDBClient.java:203), 0xFF if none; grant_ts = Grant.timestamp;
+ * grant_status = Grant.status, 0xFF for a value outside 0..254; grant_flags =
+ * MOCHI_W1G_*; sig[g] (optional, NULL = not wanted) = the 256 signature bytes,
+ * zeros without MOCHI_W1G_HAS_SIG.  Per currentCertificates entry, in map
+ * order: key and value slices of `wire`; the value has been validated as a
+ * WriteCertificate and is otherwise opaque.
+ *
+ * The arrays of a batch plug into mochi_write1_classify[_device] (resp_off =
+ * req_resp_off, resp_kind = resp_kind_out, resp_server, resp_grant_off,
+ * grant_key, grant_ts, grant_status) and, for the rounds it answers PROCEED,
+ * into mochi_write2_source (grant_bytes = wire, grant_off, grant_len, sig,
+ * cert_mg_off = req_resp_off, mg_grant_off = resp_grant_off, mg_signer).
+ *
+ * Capacity: grant_cap / cert_cap are the entries the per-grant / per-
+ * certificate arrays hold.  n_grants and n_certs (host fields) are always
+ * written, and so are the per-response arrays and both CSRs; when a capacity
+ * is too small the call returns MOCHI_EINVAL with the counts needed and
+ * touches no per-grant or per-certificate array. */
+typedef struct mochi_write1_decoded {
+  uint8_t*  resp_status;      /* [P] enum mochi_w1r_status */
+  uint8_t*  resp_kind_out;    /* [P] */
+  uint32_t* resp_server;      /* [P] */
+  uint16_t* mg_signer;        /* [P] */
+  uint64_t* resp_client_off;  /* [P] */
+  uint32_t* resp_client_len;  /* [P] */
+  uint32_t* resp_grant_off;   /* [P+1] */
+  uint32_t* resp_cert_off;    /* [P+1] */
+  uint32_t  n_grants, n_certs;   /* out */
+  uint32_t  grant_cap, cert_cap; /* in  */
+  uint64_t* grant_off;        /* [N] */
+  uint32_t* grant_len;        /* [N] */
+  uint8_t*  grant_key;        /* [N] */
+  int64_t*  grant_ts;         /* [N] */
+  uint8_t*  grant_status;     /* [N] */
+  uint8_t*  grant_flags;      /* [N] */
+  uint8_t*  sig;              /* [N][256] or NULL */
+  uint64_t* cert_key_off;     /* [C] */
+  uint32_t* cert_key_len;     /* [C] */
+  uint64_t* cert_val_off;     /* [C] */
+  uint32_t* cert_val_len;     /* [C] */
+} mochi_write1_decoded;
+
+/* Safe capacities from wire_len and n_resps alone: slices may alias, so every
+ * response is taken at the whole blob; an entry takes two bytes or more and a
+ * decoded response holds at most 64 of each kind.  Safe, not tight. */
+void mochi_write1_reply_decode_bound(uint64_t wire_len, uint32_t n_resps, uint64_t* grants, uint64_t* certs);
+
+/* Host form: every array in host memory, no context, no GPU; ids / id_off[n_ids+1]
+ * is the server-id table as mochi_write2_encode takes it (the first equal entry
+ * wins).  MOCHI_EINVAL for a response or operand slice outside its blob, a
+ * req_resp_off that is not a CSR over n_resps, a req_op_off that is not a CSR
+ * over n_ops or gives a request more than MOCHI_MAX_OPS_PER_CERT ops, a
+ * resp_kind that is no MOCHI_W1_*, or more than 2^24 responses. */
+int mochi_write1_reply_decode(const mochi_write1_replies* replies, const uint8_t* ids, const uint32_t* id_off,
+                              uint32_t n_ids, mochi_write1_decoded* out);
+
+/* Device form: every array of `replies` and `out` in DEVICE memory, the structs
+ * themselves on the host; server ids from mochi_ctx_set_server_ids
+ * (MOCHI_EINVAL without them); scratch is the context's.  The call waits once,
+ * for the two totals, applies the capacity rule on the host and returns with
+ * the emit kernels enqueued on `stream` (hipStream_t; NULL = null stream).
+ * Same arrays as the host form; the caller's own arrays (CSRs, operand slices,
+ * response slices inside `wire`) are trusted, the bytes of `wire` are not. */
+int mochi_write1_reply_decode_device(mochi_ctx* ctx, const mochi_write1_replies* replies, mochi_write1_decoded* out,
+                                     void* stream);
+/* Per-kernel device time (ms) of the last mochi_write1_reply_decode_device call
+ * made while profiling was on (mochi_ctx_set_profiling) and that emitted:
+ * [0] k_w1d_resp, [1] the entry scan, [2] k_w1d_level2, [3] k_w1d_final + the
+ * packed scan + k_w1d_offsets, [4] k_w1d_emit, [5] the signature gather.  Waits
+ * for that call.  n_kernels <= 6. */
+int mochi_ctx_read_w1_decode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n_kernels);
+
+/* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps
  * (Write2ToServerRequestHandler.handle -> processWrite2ToServer on a 2..20
  * thread pool, MochiServer.java:36-40), coalesced across threads into one

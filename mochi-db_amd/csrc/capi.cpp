@@ -15,6 +15,7 @@
 
 #include "ctx.h"
 #include "mont.h"
+#include "w1_decode.h"
 #include "w1_issue.h"
 #include "w1_reply.h"
 
@@ -792,6 +793,119 @@ int mochi_write2_encode_device(mochi_ctx* c, const mochi_write2_source* s, uint8
   if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
   new_call(c);
   return run_write2_encode_device(c, s, wire, wire_cap, msg_off, msg_len, status, wire_len, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- Write1 reply decode (the client's round) --------------------------------
+
+namespace {
+
+int check_write1_replies(const mochi_write1_replies* r, const mochi_write1_decoded* o) {
+  if (!r || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (!o->resp_grant_off || !o->resp_cert_off) return fail(MOCHI_EINVAL, "resp_grant_off / resp_cert_off required");
+  if (r->n_resps && (!r->resp_off || !r->resp_len || !r->resp_kind || (!r->wire && r->wire_len)))
+    return fail(MOCHI_EINVAL, "wire / resp_off / resp_len / resp_kind required");
+  if (r->n_resps && (!o->resp_status || !o->resp_kind_out || !o->resp_server || !o->mg_signer || !o->resp_client_off ||
+                     !o->resp_client_len))
+    return fail(MOCHI_EINVAL, "the per-response outputs are required");
+  if (r->n_resps && !r->n_reqs) return fail(MOCHI_EINVAL, "responses without a request");
+  if (r->n_reqs && (!r->req_resp_off || !r->req_op_off)) return fail(MOCHI_EINVAL, "req_resp_off / req_op_off required");
+  if (r->n_ops && (!r->op_key_off || !r->op_key_len || (!r->strings && r->strings_len)))
+    return fail(MOCHI_EINVAL, "strings / op_key_off / op_key_len required");
+  if (r->n_resps > mochi::w1d::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
+  if (o->grant_cap && (!o->grant_off || !o->grant_len || !o->grant_key || !o->grant_ts || !o->grant_status ||
+                       !o->grant_flags))
+    return fail(MOCHI_EINVAL, "the per-grant outputs are required (grant_cap > 0)");
+  if (o->cert_cap && (!o->cert_key_off || !o->cert_key_len || !o->cert_val_off || !o->cert_val_len))
+    return fail(MOCHI_EINVAL, "the per-certificate outputs are required (cert_cap > 0)");
+  return MOCHI_OK;
+}
+
+int w1d_capacity_error(const mochi_write1_decoded* o) {
+  return fail(MOCHI_EINVAL, "grant_cap (%u) / cert_cap (%u) smaller than the decoded grants (%u) / certificates (%u)",
+              o->grant_cap, o->cert_cap, o->n_grants, o->n_certs);
+}
+
+int run_write1_decode_device(mochi_ctx* c, const mochi_write1_replies* r, mochi_write1_decoded* o, hipStream_t st) {
+  if (c->n_ids != c->n_keys) return fail(MOCHI_EINVAL, "server ids not set (mochi_ctx_set_server_ids)");
+  o->n_grants = o->n_certs = 0;
+  const uint32_t P = r->n_resps;
+  EncState& x = c->w1d;
+  if (P == 0) {  // both CSRs hold their one element
+    x.ev_valid = false;
+    HIP_TRY(hipMemsetAsync(o->resp_grant_off, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(o->resp_cert_off, 0, 4, st));
+    return MOCHI_OK;
+  }
+  mochi::W1DecArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.in = *r;
+  a.v.ids = c->ids.as<uint8_t>();
+  a.v.id_off = c->id_off.as<uint32_t>();
+  a.v.n_ids = c->n_ids;
+  a.v.out = *o;
+  a.P = P;
+  int rc = x.begin(a, mochi::w1d_layout, P + 1, 8, c->profiling, mochi::kW1DecEvents);
+  if (rc) return rc;
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_w1d_count(a, st));
+  if ((rc = x.fetch_totals(a.off64 + P, 8, c->ev_tot, st))) return rc;
+  const uint64_t tot = *(const uint64_t*)x.tot.p;
+  o->n_grants = (uint32_t)tot;
+  o->n_certs = (uint32_t)(tot >> 32);
+  const bool fits = o->n_grants <= o->grant_cap && o->n_certs <= o->cert_cap;
+  if (fits) {
+    if (o->sig && o->n_grants) {
+      if ((rc = c->w1d_sig.ensure(8 * (size_t)o->n_grants))) return rc;
+      a.v.sig_src = c->w1d_sig.as<uint64_t>();
+    }
+    HIP_TRY(mochi::launch_w1d_emit(a, o->n_grants, st));
+  }
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(c->order.release(st));
+  return fits ? MOCHI_OK : w1d_capacity_error(o);
+}
+
+}  // namespace
+
+extern "C" {
+
+void mochi_write1_reply_decode_bound(uint64_t wire_len, uint32_t n_resps, uint64_t* grants, uint64_t* certs) {
+  const uint64_t per = wire_len / 2 < mochi::w1d::kMaxEntries ? wire_len / 2 : mochi::w1d::kMaxEntries;
+  if (grants) *grants = per * n_resps;
+  if (certs) *certs = per * n_resps;
+}
+
+int mochi_write1_reply_decode(const mochi_write1_replies* r, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids,
+                              mochi_write1_decoded* o) {
+  int rc = check_write1_replies(r, o);
+  if (rc) return rc;
+  if (n_ids && (!ids || !id_off)) return fail(MOCHI_EINVAL, "ids / id_off required");
+  const char* err = nullptr;
+  rc = mochi_host::write1_reply_decode(r, ids, id_off, n_ids, o, &err);
+  if (rc && err) return fail(rc, "mochi_write1_reply_decode: %s", err);
+  return rc ? w1d_capacity_error(o) : MOCHI_OK;
+}
+
+int mochi_write1_reply_decode_device(mochi_ctx* c, const mochi_write1_replies* r, mochi_write1_decoded* o,
+                                     void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  int rc = check_write1_replies(r, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  return run_write1_decode_device(c, r, o, (hipStream_t)stream);
+}
+
+int mochi_ctx_read_w1_decode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n_kernels) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  static const int kSpan[mochi::kW1DecStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {5, 6}, {6, 7}};
+  return c->w1d.read_profile(kSpan, mochi::kW1DecStages, kernel_ms, n_kernels,
+                             "no Write1 reply decode call was made while profiling was on");
 }
 
 int mochi_fold_matrix(const uint8_t* modulus_be, int8_t* img, uint32_t* cadd) {

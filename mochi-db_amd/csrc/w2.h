@@ -114,5 +114,7 @@ hipError_t launch_w2_count(const W2Args& a, hipStream_t stream);  // + exclusive
 hipError_t launch_w2_emit(const W2Args& a, hipStream_t stream);
 hipError_t launch_w2_fixup(const W2Args& a, uint32_t* accept_bits, uint8_t* reason, uint8_t* fail_op,
                            uint8_t* op_decision, uint32_t* op_g0, int64_t* op_ts, hipStream_t stream);
+// k_w2_sig alone: sig[g] = wire[sig_src[g] .. +256), zeros where sig_src[g] is ~0 (16 lanes per signature)
+hipError_t launch_w2_sig(const uint8_t* wire, const uint64_t* sig_src, uint32_t N, uint8_t* sig, hipStream_t stream);
 
 }  // namespace mochi

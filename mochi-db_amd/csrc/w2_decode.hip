@@ -1905,6 +1905,12 @@ hipError_t launch_w2_fixup(const W2Args& a, uint32_t* accept_bits, uint8_t* reas
   return hipGetLastError();
 }
 
+// k_w2_sig for the Write1 reply decoder (w1_decode.h), which gathers its signatures the same way
+hipError_t launch_w2_sig(const uint8_t* wire, const uint64_t* sig_src, uint32_t N, uint8_t* sig, hipStream_t st) {
+  if (N) hipLaunchKernelGGL(k_w2_sig, dim3(cdiv((uint64_t)N * 16, 256)), dim3(256), 0, st, wire, sig_src, N, sig);
+  return hipGetLastError();
+}
+
 }  // namespace mochi
 
 #if MOCHI_W2_STAMPS

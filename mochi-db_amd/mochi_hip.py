@@ -205,6 +205,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_write1_reply_encode.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp]
     lib.mochi_write1_reply_encode_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
     lib.mochi_signer_read_reply_profile.argtypes = [vp, vp, u32]
+    lib.mochi_write1_reply_decode_bound.restype = None
+    lib.mochi_write1_reply_decode_bound.argtypes = [u64, u32, vp, vp]
+    lib.mochi_write1_reply_decode.argtypes = [vp, vp, vp, u32, vp]
+    lib.mochi_write1_reply_decode_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_ctx_read_w1_decode_profile.argtypes = [vp, vp, u32]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -554,6 +559,28 @@ class Verifier:
         if self.lib.mochi_ctx_read_encode_profile(self.ctx, _ptr(ms), ms.size) != OK:
             raise MochiError(f"mochi_ctx_read_encode_profile: {_err(self.lib)}")
         return dict(zip(self.ENCODE_KERNELS, (float(x) for x in ms)))
+
+    def write1_reply_decode_device(self, dreplies: "DeviceWrite1Replies", out: "DeviceWrite1Decoded", stream: int = 0,
+                                   check: bool = True) -> int:
+        """mochi_write1_reply_decode_device: device-resident Write1 reply bodies -> the
+        arrays of `out` (server ids from set_server_ids).  Waits for the two totals
+        (out.n_grants / out.n_certs), then returns the rc with the emit kernels enqueued
+        on `stream`: EINVAL when a capacity of `out` is too small (the counts needed are
+        set, no per-grant or per-certificate array touched; raises then if `check`)."""
+        r, o = dreplies.to_c(), out.to_c()
+        rc = self.lib.mochi_write1_reply_decode_device(self.ctx, ctypes.addressof(r), ctypes.addressof(o), stream or None)
+        out.n_grants, out.n_certs = int(o.n_grants), int(o.n_certs)
+        short = rc == EINVAL and (out.n_grants > out.grant_cap or out.n_certs > out.cert_cap)
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_write1_reply_decode_device rc={rc}: {_err(self.lib)}")
+        return rc
+
+    def read_w1_decode_profile(self) -> dict:
+        """Per-kernel ms of the last write1_reply_decode_device call made with set_profiling(True)."""
+        ms = np.zeros(len(W1_DECODE_STAGES), np.float32)
+        if self.lib.mochi_ctx_read_w1_decode_profile(self.ctx, _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_w1_decode_profile: {_err(self.lib)}")
+        return dict(zip(W1_DECODE_STAGES, (float(x) for x in ms)))
 
     def decode_write2(self, wb) -> dict:
         """The device decoder's SoA view of the messages (inspection / tests)."""
@@ -1816,6 +1843,227 @@ class DeviceWrite1ReplySource:
             setattr(c, k, None if t is None else t.data_ptr())
         return c
 
+
+
+# ---------------------------------------------------------------------------
+# Write1 reply decode (the client's round): Write1OkFromServer /
+# Write1RefusedFromServer bodies -> the arrays write1_classify and Write2Source read
+# ---------------------------------------------------------------------------
+W1R_OK, W1R_MALFORMED, W1R_FALLBACK, W1R_UNKNOWN_SERVER = range(4)
+W1G_HAS_SIG, W1G_KEY_DIFFERS = 0x01, 0x02
+W1_DECODE_STAGES = ("k_w1d_resp", "entry_scan", "k_w1d_level2", "final_scan_offsets", "k_w1d_emit", "signatures")
+
+
+class Write1Replies_C(ctypes.Structure):
+    _fields_ = [("n_resps", ctypes.c_uint32), ("n_reqs", ctypes.c_uint32), ("n_ops", ctypes.c_uint32),
+                ("_pad0", ctypes.c_uint32), ("wire", ctypes.c_void_p), ("wire_len", ctypes.c_uint64),
+                ("resp_off", ctypes.c_void_p), ("resp_len", ctypes.c_void_p), ("resp_kind", ctypes.c_void_p),
+                ("req_resp_off", ctypes.c_void_p), ("strings", ctypes.c_void_p), ("strings_len", ctypes.c_uint64),
+                ("req_op_off", ctypes.c_void_p), ("op_key_off", ctypes.c_void_p), ("op_key_len", ctypes.c_void_p)]
+
+
+class Write1Decoded_C(ctypes.Structure):
+    _fields_ = [("resp_status", ctypes.c_void_p), ("resp_kind_out", ctypes.c_void_p), ("resp_server", ctypes.c_void_p),
+                ("mg_signer", ctypes.c_void_p), ("resp_client_off", ctypes.c_void_p),
+                ("resp_client_len", ctypes.c_void_p), ("resp_grant_off", ctypes.c_void_p),
+                ("resp_cert_off", ctypes.c_void_p), ("n_grants", ctypes.c_uint32), ("n_certs", ctypes.c_uint32),
+                ("grant_cap", ctypes.c_uint32), ("cert_cap", ctypes.c_uint32), ("grant_off", ctypes.c_void_p),
+                ("grant_len", ctypes.c_void_p), ("grant_key", ctypes.c_void_p), ("grant_ts", ctypes.c_void_p),
+                ("grant_status", ctypes.c_void_p), ("grant_flags", ctypes.c_void_p), ("sig", ctypes.c_void_p),
+                ("cert_key_off", ctypes.c_void_p), ("cert_key_len", ctypes.c_void_p),
+                ("cert_val_off", ctypes.c_void_p), ("cert_val_len", ctypes.c_void_p)]
+
+
+# output arrays by what they are indexed with: "P" responses, "P1" the CSRs, "N" grants, "C" certificates
+_W1D_OUT = dict(resp_status=(np.uint8, "P"), resp_kind_out=(np.uint8, "P"), resp_server=(np.uint32, "P"),
+                mg_signer=(np.uint16, "P"), resp_client_off=(np.uint64, "P"), resp_client_len=(np.uint32, "P"),
+                resp_grant_off=(np.uint32, "P1"), resp_cert_off=(np.uint32, "P1"),
+                grant_off=(np.uint64, "N"), grant_len=(np.uint32, "N"), grant_key=(np.uint8, "N"),
+                grant_ts=(np.int64, "N"), grant_status=(np.uint8, "N"), grant_flags=(np.uint8, "N"),
+                cert_key_off=(np.uint64, "C"), cert_key_len=(np.uint32, "C"), cert_val_off=(np.uint64, "C"),
+                cert_val_len=(np.uint32, "C"))
+
+
+@dataclass
+class Write1Replies:
+    """The Write1 reply bodies a client received (mochi_write1_replies, host arrays)."""
+
+    wire: np.ndarray  # uint8
+    resp_off: np.ndarray  # uint64 [P]
+    resp_len: np.ndarray  # uint32 [P]
+    resp_kind: np.ndarray  # uint8 [P] W1_*
+    req_resp_off: np.ndarray  # uint32 [Q+1]
+    strings: np.ndarray  # uint8: the operands the client sent
+    req_op_off: np.ndarray  # uint32 [Q+1]
+    op_key_off: np.ndarray  # uint64 [O]
+    op_key_len: np.ndarray  # uint32 [O]
+
+    DTYPES = dict(wire=np.uint8, resp_off=np.uint64, resp_len=np.uint32, resp_kind=np.uint8, req_resp_off=np.uint32,
+                  strings=np.uint8, req_op_off=np.uint32, op_key_off=np.uint64, op_key_len=np.uint32)
+
+    @property
+    def n_resps(self) -> int:
+        return int(np.asarray(self.resp_off).shape[0])
+
+    @property
+    def n_reqs(self) -> int:
+        return int(np.asarray(self.req_resp_off).shape[0]) - 1
+
+    @property
+    def n_ops(self) -> int:
+        return int(np.asarray(self.op_key_off).shape[0])
+
+    def arrays(self) -> dict:
+        return {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write1Replies_C()
+        c.n_resps, c.n_reqs, c.n_ops = self.n_resps, self.n_reqs, self.n_ops
+        c.wire_len, c.strings_len = int(arrs["wire"].size), int(arrs["strings"].size)
+        for k, a in arrs.items():
+            if a.size == 0:  # an empty array still gets a valid address
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+@dataclass
+class Write1Decoded:
+    """Outputs of write1_reply_decode (mochi_write1_decoded): the caller's buffers, whole
+    (n_grants / n_certs say how much of the per-grant / per-certificate ones is meant)."""
+
+    rc: int
+    n_grants: int
+    n_certs: int
+    arrays: dict  # name -> array, names as in mochi_write1_decoded; "sig" [cap, 256] or absent
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def trimmed(self) -> dict:
+        """Every array cut to its meaning (per-grant / per-certificate ones to 0 unless rc is OK)."""
+        P = self.arrays["resp_status"].shape[0]
+        n = dict(P=P, P1=P + 1, N=self.n_grants if self.rc == OK else 0, C=self.n_certs if self.rc == OK else 0)
+        out = {k: self.arrays[k][:n[w]] for k, (dt, w) in _W1D_OUT.items()}
+        if "sig" in self.arrays:
+            out["sig"] = self.arrays["sig"][:n["N"]]
+        return out
+
+
+def write1_reply_decode_bound(wire_len: int, n_resps: int):
+    """mochi_write1_reply_decode_bound: safe (grant, certificate) capacities."""
+    g, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    load_library().mochi_write1_reply_decode_bound(int(wire_len), int(n_resps), ctypes.addressof(g), ctypes.addressof(c))
+    return int(g.value), int(c.value)
+
+
+def write1_reply_decode_into(replies: "Write1Replies", server_ids, grant_cap: int, cert_cap: int, want_sig: bool = True,
+                             fill: int = 0) -> "Write1Decoded":
+    """mochi_write1_reply_decode into buffers of the given capacities, prefilled with
+    `fill`.  rc is EINVAL with n_grants / n_certs = the counts needed when one is too
+    small (no per-grant or per-certificate array touched); any other failure raises."""
+    lib = load_library()
+    r, keep = replies.to_c()
+    ids, id_off, n_ids = _id_table(server_ids)
+    P = replies.n_resps
+    n = dict(P=P, P1=P + 1, N=int(grant_cap), C=int(cert_cap))
+    arr = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _W1D_OUT.items()}
+    if want_sig:
+        arr["sig"] = np.full((int(grant_cap), RSA_BYTES), fill, np.uint8)
+    o = Write1Decoded_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a) if a.size else None)
+    o.grant_cap, o.cert_cap = int(grant_cap), int(cert_cap)
+    rc = lib.mochi_write1_reply_decode(ctypes.addressof(r), _ptr(ids), _ptr(id_off), n_ids, ctypes.addressof(o))
+    if rc != OK and not (rc == EINVAL and (o.n_grants > grant_cap or o.n_certs > cert_cap)):
+        raise MochiError(f"mochi_write1_reply_decode rc={rc}: {_err(lib)}")
+    return Write1Decoded(rc=rc, n_grants=int(o.n_grants), n_certs=int(o.n_certs), arrays=arr)
+
+
+def write1_reply_decode(replies: "Write1Replies", server_ids, want_sig: bool = True) -> "Write1Decoded":
+    """Host form of the Write1 reply decoder: counts first, then into buffers of exactly
+    the sizes needed."""
+    first = write1_reply_decode_into(replies, server_ids, 0, 0, want_sig)
+    if first.rc == OK:
+        return first
+    return write1_reply_decode_into(replies, server_ids, first.n_grants, first.n_certs, want_sig)
+
+
+class DeviceWrite1Replies:
+    """A Write1Replies copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, replies: "Write1Replies", device: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: np.uint8, np.uint32: np.int32, np.uint64: np.int64}
+        t = {k: torch.from_numpy((a if a.size else np.zeros(1, a.dtype)).view(sv[Write1Replies.DTYPES[k]])).to(dev)
+             for k, a in replies.arrays().items()}
+        self._set(replies.n_resps, replies.n_reqs, replies.n_ops, int(np.asarray(replies.wire).size),
+                  int(np.asarray(replies.strings).size), t)
+
+    def _set(self, P, Q, O, wire_len, strings_len, tensors):
+        self.n_resps, self.n_reqs, self.n_ops, self.wire_len, self.strings_len = int(P), int(Q), int(O), int(wire_len), \
+            int(strings_len)
+        for k in Write1Replies.DTYPES:
+            setattr(self, k, tensors[k])
+
+    @classmethod
+    def from_tensors(cls, n_resps: int, n_reqs: int, n_ops: int, **tensors) -> "DeviceWrite1Replies":
+        """Arrays already on the device (uint64 as int64, uint32 as int32), used as they are."""
+        self = cls.__new__(cls)
+        self._set(n_resps, n_reqs, n_ops, tensors["wire"].numel(), tensors["strings"].numel(), tensors)
+        return self
+
+    def to_c(self) -> Write1Replies_C:
+        c = Write1Replies_C()
+        c.n_resps, c.n_reqs, c.n_ops = self.n_resps, self.n_reqs, self.n_ops
+        c.wire_len, c.strings_len = self.wire_len, self.strings_len
+        for k in Write1Replies.DTYPES:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
+
+
+class DeviceWrite1Decoded:
+    """Device buffers for the outputs of Verifier.write1_reply_decode_device, prefilled with
+    `fill`; n_grants / n_certs are set by the call.  Tensors carry the ABI widths (uint16 as
+    int16, uint32 as int32, uint64 as int64)."""
+
+    def __init__(self, n_resps: int, grant_cap: int, cert_cap: int, want_sig: bool = True, device: int = 0,
+                 fill: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint32: torch.int32, np.uint64: torch.int64,
+              np.int64: torch.int64}
+        self.n_resps, self.grant_cap, self.cert_cap = int(n_resps), int(grant_cap), int(cert_cap)
+        n = dict(P=self.n_resps, P1=self.n_resps + 1, N=self.grant_cap, C=self.cert_cap)
+        pat = lambda dt: int.from_bytes(bytes([fill & 0xFF]) * np.dtype(dt).itemsize, "little", signed=dt != np.uint8)
+        for k, (dt, w) in _W1D_OUT.items():
+            setattr(self, k, torch.full((max(n[w], 1),), pat(dt), dtype=sv[dt], device=dev))
+        self.sig = torch.full((max(self.grant_cap, 1), RSA_BYTES), fill & 0xFF, dtype=torch.uint8, device=dev) \
+            if want_sig else None
+        self.n_grants = self.n_certs = 0
+
+    def to_c(self) -> Write1Decoded_C:
+        o = Write1Decoded_C()
+        for k in _W1D_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        o.sig = None if self.sig is None else self.sig.data_ptr()
+        o.grant_cap, o.cert_cap = self.grant_cap, self.cert_cap
+        return o
+
+    def to_host(self, rc: int = OK) -> "Write1Decoded":
+        """The buffers on the host, whole (as write1_reply_decode_into returns them)."""
+        n = dict(P=self.n_resps, P1=self.n_resps + 1, N=self.grant_cap, C=self.cert_cap)
+        arr = {k: getattr(self, k).cpu().numpy().view(dt)[:n[w]] for k, (dt, w) in _W1D_OUT.items()}
+        if self.sig is not None:
+            arr["sig"] = self.sig.cpu().numpy()[:self.grant_cap]
+        return Write1Decoded(rc=rc, n_grants=self.n_grants, n_certs=self.n_certs, arrays=arr)
 
 
 # ---------------------------------------------------------------------------
