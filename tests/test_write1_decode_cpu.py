@@ -1,7 +1,9 @@
 """Write1 reply decoder, host form (mochi_write1_reply_decode): array for array equal to
 the plain-Python model (write1_decode_model, itself cross-checked against
 google.protobuf) on every body the reply encoder produces and on a mutation corpus; the
-round trip of the reply encoder's inputs; what the corpus covers; the capacity rule;
+round trip of the reply encoder's inputs; what the corpus covers; the bodies and batches
+the GPU tests use at the device form's launch edges (heavy bodies, the level-2 pattern,
+requests without responses or ops, a signature ending the wire); the capacity rule;
 argument errors."""
 import numpy as np
 import pytest
@@ -133,6 +135,109 @@ def test_corpus_reaches_every_status_and_flag(corpus_batch):
     bad = np.isin(want["resp_status"], [mh.W1R_MALFORMED, mh.W1R_FALLBACK])
     assert (want["resp_kind_out"][bad] == mh.W1_OTHER).all()
     assert (want["resp_kind_out"][~bad] == corpus_batch.resp_kind[~bad]).all()
+
+
+def test_corpus_signature_sources_cover_every_residue(corpus_batch):
+    """The signature gather reads whole 16-byte chunks: every position of a source in its chunk occurs."""
+    src = DM.sig_sources(corpus_batch, DM.decode(corpus_batch, DM.IDS))
+    assert {s % 16 for s in src} == set(range(16))
+
+
+# 3b. the bodies and batches of the device form's launch edges -------------------------------
+def test_heavy_bodies_have_the_status_their_name_says():
+    ec = DM.edge_cases()
+    st = {n: DM.decode_body(c.body).status for n, c in ec.items()}
+    assert st["ok:heavy"] == st["ok:heavy_light"] == st["ok:heavy_no_sig"] == mh.W1R_OK
+    assert st["mal:heavy_bad_63"] == st["mal:heavy_bad_0_and_63"] == st["mal:heavy_bad_31_and_32"] == mh.W1R_MALFORMED
+    assert st["fb:heavy"] == mh.W1R_FALLBACK
+    assert st["mal:heavy_fb_and_bad_0"] == mh.W1R_MALFORMED  # MALFORMED wins over FALLBACK
+    assert st["mal:level1_one_byte"] == mh.W1R_MALFORMED and st["fb:level1_two_multigrants"] == mh.W1R_FALLBACK
+    assert DM.decode_body(DM.SMALL_BAD).status == mh.W1R_MALFORMED
+    d = DM.decode_body(ec["ok:heavy"].body)
+    assert len(d.grants) == 1 and d.grants[0].flags == mh.W1G_HAS_SIG and len(d.certs) == DM.MAX_ENTRIES
+    # what the level-2 grid sees of them: the heavy bodies whatever their status, nothing of the rest
+    ne = {n: DM.level2_entries(c.body, c.kind) for n, c in ec.items()}
+    assert all(ne[n] == (0 if n.startswith("kind:") or "level1" in n else 6 if n == "ok:heavy_no_sig" else 65) for n in ne)
+
+
+def test_heavy_bodies_agree_with_google_protobuf():
+    pytest.importorskip("google.protobuf")
+    last = DM.Case("sig_last", DM.reply(DM.multigrant([(DM.K1, DM.grant(DM.K1, 11))])), (DM.K1,))
+    bodies = {c.body for c in tuple(DM.edge_cases().values()) + DM.far_cases() + (last,)}
+    for r in (DM.grouping_batch(), DM.cap_batch(4, DM.SMALL_BAD)):
+        wire = r.wire.tobytes()
+        bodies |= {wire[int(o):int(o) + int(n)] for o, n in zip(r.resp_off, r.resp_len)}
+    assert len(bodies) > 40
+    for b in sorted(bodies):
+        DM.crosscheck(b, DM.decode_body(b))
+
+
+@pytest.mark.parametrize("layout", ["packed", "shared"])
+@pytest.mark.parametrize("P", [4, 12, 300])
+def test_level2_pattern_equals_the_model(P, layout):
+    cases = (DM.edge_cases()["ok:heavy"],) * 3 + (DM.edge_cases()["mal:heavy_bad_63"],) if P == 4 else DM.pattern_cases(P)
+    r = DM.batch(cases, layout=layout, per_req=3)
+    got, want = check(r, DM.IDS, f"pattern {P} {layout}")
+    st = want["resp_status"].tolist()
+    if P == 4:
+        assert st == [mh.W1R_OK] * 3 + [mh.W1R_MALFORMED]
+    else:
+        M, F, K = mh.W1R_MALFORMED, mh.W1R_FALLBACK, mh.W1R_OK
+        assert st[:12] == [K, M, K, K, K, K, M, F, M, F, M, K]  # an unparsed kind is OK and keeps its kind
+        assert want["resp_kind_out"][:6].tolist() == [mh.W1_REQUEST_FAILED, mh.W1_OTHER, mh.W1_OK, mh.W1_OTHER,
+                                                      mh.W1_REQUEST_FAILED, mh.W1_OTHER]
+    heavy = sum(c.name.split(":")[1].startswith("heavy") for c in cases)
+    assert DM.n_level2_entries(r) == 65 * heavy
+
+
+def test_cap_batch_equals_the_model_at_a_small_size():
+    """The block-cap batch's builder, at a size the model decodes in no time."""
+    for last in (DM.SMALL_BAD, DM.heavy(bad=63)):
+        r = DM.cap_batch(40, last)
+        got, want = check(r, DM.IDS, "cap")
+        assert want["resp_status"].tolist() == [mh.W1R_OK] * 39 + [mh.W1R_MALFORMED]
+        assert DM.n_level2_entries(r) == 2 * 39 + DM.level2_entries(last)
+        assert len(set(r.resp_off.tolist())) == 2 and np.diff(r.req_resp_off.astype(np.int64)).tolist() == [1, 12, 7, 18, 2]
+
+
+def test_request_grouping_equals_the_model():
+    r = DM.grouping_batch()
+    got, want = check(r, DM.IDS, "grouping")
+    n_resp = np.diff(r.req_resp_off.astype(np.int64)).tolist()
+    n_ops = np.diff(r.req_op_off.astype(np.int64)).tolist()
+    assert n_resp == [0, 2, 0, 0, 3, 3, 1, 0] and n_ops == [1, 2, 0, 1, 0, 64, 2, 1]
+    assert (want["resp_status"] == mh.W1R_OK).all()
+    keys = lambda q: [int(k) for p in range(int(r.req_resp_off[q]), int(r.req_resp_off[q + 1]))
+                      for k in want["grant_key"][int(want["resp_grant_off"][p]):int(want["resp_grant_off"][p + 1])]]
+    assert keys(1) == [0, 0xFF, 0xFF]  # alpha; key-A and key-B are not this request's
+    assert keys(4) == [0xFF] * 5  # a request without ops
+    assert keys(5) == [0, 63, 0xFF, 63, 0, 63]  # key-A at slots 0 and 7: the first; key-B at the last slot alone
+    assert keys(6) == [1]
+
+
+@pytest.mark.parametrize("lead", [0, 5])
+def test_signature_ends_the_wire(lead):
+    """No filler after the last body, whose last field is its signature: the last 256 bytes of the wire."""
+    by = {c.name: c for c in DM.corpus()}
+    last = DM.Case("sig_last", DM.reply(DM.multigrant([(DM.K1, DM.grant(DM.K1, 11))])), (DM.K1,))
+    r = DM.batch((by["rep:sigs"], by["mutate:2"], last), per_req=2, lead=lead, tail=0)
+    assert int(r.resp_off[-1]) + int(r.resp_len[-1]) == r.wire.size
+    got, want = check(r, DM.IDS, "wire end")
+    assert want["grant_flags"][-1] == mh.W1G_HAS_SIG
+    np.testing.assert_array_equal(want["sig"][-1], r.wire[-256:])
+    assert DM.sig_sources(r, want)[-1] == r.wire.size - 256
+
+
+def test_far_cases_cover_what_the_offset_test_needs():
+    cases = DM.far_cases()
+    r = DM.batch(cases, per_req=3, mod=16)
+    got, want = check(r, DM.IDS, "far")
+    assert r.wire.size <= 64 << 10 and {int(o) % 16 for o in r.resp_off} == set(range(16))
+    assert {s % 16 for s in DM.sig_sources(r, want)} == set(range(16))
+    assert len(cases) == 32 and set(want["resp_status"].tolist()) == {0, 1, 2, 3}
+    assert {mh.W1_REQUEST_FAILED, mh.W1_OTHER, mh.W1_REFUSED} <= {c.kind for c in cases}
+    assert {int(f) & mh.W1G_HAS_SIG for f in want["grant_flags"]} == {0, mh.W1G_HAS_SIG}
+    assert (want["resp_client_len"] > 0).any() and len(want["cert_key_off"]) > 64
 
 
 # 4. the capacity rule ---------------------------------------------------------------------

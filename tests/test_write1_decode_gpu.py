@@ -5,7 +5,9 @@ empty-batch edges of its launch sequence; optional outputs; the capacity rule; t
 streams agree; the profile; and the client's round with no Python parsing -- four
 servers' replies decoded, classified, assembled into Write2ToServer bodies and
 accepted by the verifier -- with a second batch whose decisions equal the client
-model's."""
+model's; and the parts only the device form has, at their edges: later passes of the
+grid-stride level-2 kernel and its block cap, wire offsets past 4 GiB, requests without
+responses or ops, a signature that ends the wire, scratch that grows between streams."""
 
 import numpy as np
 import pytest
@@ -42,29 +44,39 @@ def corpus_batch():
     return DM.batch(DM.corpus())
 
 
-def _decode_device(ver, replies, grant_cap, cert_cap, want_sig=True, stream=None, check=True):
+def _decode_device(ver, replies, grant_cap, cert_cap, want_sig=True, stream=None, check=True, dr=None):
+    """dr: the batch already on the device (`replies` is not read then)."""
     import torch
 
     s = stream or torch.cuda.Stream()
-    dr = mh.DeviceWrite1Replies(replies, 0)
-    out = mh.DeviceWrite1Decoded(replies.n_resps, grant_cap, cert_cap, want_sig, fill=FILL)
+    dr = dr or mh.DeviceWrite1Replies(replies, 0)
+    out = mh.DeviceWrite1Decoded(dr.n_resps, grant_cap, cert_cap, want_sig, fill=FILL)
     torch.cuda.synchronize()  # uploads and fills went to the current stream
     rc = ver.write1_reply_decode_device(dr, out, stream=s.cuda_stream, check=check)
     torch.cuda.synchronize()
     return out.to_host(rc)
 
 
-def _device_equals_host(ver, replies, ids, slack=3, want_sig=True):
-    host = mh.write1_reply_decode(replies, ids, want_sig)
-    N, C = host.n_grants, host.n_certs
-    got = _decode_device(ver, replies, N + slack, C + slack, want_sig)
+def _assert_decoded(got, want, N, C, want_sig=True):
+    """The guard-filled device outputs `got` hold the trimmed arrays `want` and nothing else."""
     assert got.rc == mh.OK and (got.n_grants, got.n_certs) == (N, C)
-    DM.assert_equal(got.trimmed(), host.trimmed())
+    DM.assert_equal(got.trimmed(), want)
     for k, (dt, w) in mh._W1D_OUT.items():  # nothing past the counts is written
         if w in ("N", "C"):
             assert (got.arrays[k][N if w == "N" else C:].view(np.uint8) == FILL).all(), k
     if want_sig:
         assert (got.arrays["sig"][N:] == FILL).all()
+
+
+def _device_equals_host(ver, replies, ids, slack=3, want_sig=True, model=False):
+    """model: the device outputs also equal the Python model's, compared directly."""
+    host = mh.write1_reply_decode(replies, ids, want_sig)
+    N, C = host.n_grants, host.n_certs
+    got = _decode_device(ver, replies, N + slack, C + slack, want_sig)
+    _assert_decoded(got, host.trimmed(), N, C, want_sig)
+    if model:
+        want = DM.decode(replies, ids)
+        DM.assert_equal(got.trimmed(), want if want_sig else {k: v for k, v in want.items() if k != "sig"})
     return host
 
 
@@ -307,3 +319,152 @@ def test_classifier_on_a_mixed_batch_equals_the_client_model(pems):
     assert decision.tolist() == model
     assert model[1] == mh.W1_THROW_REFUSED and model[2] == mh.W1_THROW_REFUSED and model[3] == mh.W1_RETRY
     assert all(model[q] == mh.W1_PROCEED for q in (0, 4, 5, 6, 7))
+
+
+# 6. the level-2 grid: later passes of the grid-stride loop, the block cap ----------------------
+def _l2_lanes(P):
+    """Lanes of k_w1d_level2's grid: w1_decode.hip's l2_blocks(P) blocks, clamp(ceil(2P / 256), 1, 4096), of 256."""
+    return 256 * min(max(-(-2 * P // 256), 1), 4096)
+
+
+def _entry_bases(cases):
+    """Index of each response's first level-2 entry, and the total last (from the model)."""
+    return np.concatenate([[0], np.cumsum([DM.level2_entries(c.body, c.kind) for c in cases])]).tolist()
+
+
+# shape -> (cases, full passes the entries exceed, a response whose entries all lie past the first pass but for its first `head`)
+def _l2_shape(shape):
+    ec = DM.edge_cases()
+    if shape == "4_ok":  # the smallest second pass: 260 entries on 256 lanes (the four entries left are valid)
+        return (ec["ok:heavy"],) * 4, 1, None
+    if shape == "4_last_bad":  # ... and the last of them, entry 259, is the MALFORMED one
+        return (ec["ok:heavy"],) * 3 + (ec["mal:heavy_bad_63"],), 1, None
+    P = int(shape)
+    return DM.pattern_cases(P), {12: 1, 300: 10}[P], 10  # response 10, bad at 0 and 63: entries 260..324
+
+
+@pytest.mark.parametrize("layout", ["packed", "shared"])
+@pytest.mark.parametrize("shape", ["4_ok", "4_last_bad", "12", "300"])
+def test_level2_later_passes(ver, shape, layout):
+    cases, passes, late = _l2_shape(shape)
+    P, lanes, base = len(cases), _l2_lanes(len(cases)), _entry_bases(cases)
+    # the preconditions, from the model: without them the test would pass without a later pass
+    assert base[-1] > passes * lanes, (base[-1], lanes)
+    if shape == "4_last_bad":
+        assert base[3] + 64 >= lanes  # certificate entry 63 of response 3
+    if late is not None:
+        assert base[late] >= 256 and base[late + 1] - base[late] == 65 and base[late - 1] == base[late]
+        assert base[1] == base[2] == 0 and base[3] == base[6] and base[11] == base[12]  # runs without entries
+    if P == 300:
+        assert lanes == 3 * 256
+    r = DM.batch(cases, layout=layout, per_req=3)
+    assert DM.n_level2_entries(r) == base[-1]
+    host = _device_equals_host(ver, r, DM.IDS, model=P <= 12)
+    st = host.arrays["resp_status"]
+    assert st.tolist()[:P] == [{"ok": mh.W1R_OK, "mal": mh.W1R_MALFORMED, "fb": mh.W1R_FALLBACK, "kind": mh.W1R_OK}
+                               [c.name.split(":")[0]] for c in cases]
+
+
+@pytest.mark.parametrize("P, last, second_pass", [(524288, "small", False), (524289, "small", True), (524289, "heavy", True)])
+def test_level2_block_cap(ver, P, last, second_pass):
+    """4096 blocks: P = 524,288 fills them without the cap (2 entries a response, one pass);
+    at P = 524,289 the cap holds and block 0 takes the last response's entries in a second
+    pass.  The last response alone is MALFORMED, in its last entry."""
+    body = DM.SMALL_BAD if last == "small" else DM.edge_cases()["mal:heavy_bad_63"].body
+    r = DM.cap_batch(P, body)
+    lanes, n = _l2_lanes(P), DM.n_level2_entries(r)
+    assert lanes == 4096 * 256 == _l2_lanes(P + 1000) and n == 2 * (P - 1) + DM.level2_entries(body)
+    assert (n > lanes) == second_pass and (second_pass or n == lanes)
+    assert not second_pass or 2 * (P - 1) == lanes  # the last response's entries, and only they, are the second pass
+    host = _device_equals_host(ver, r, DM.IDS, want_sig=False)
+    st = host.arrays["resp_status"]
+    assert st[-1] == mh.W1R_MALFORMED and (st[:-1] == mh.W1R_OK).all()
+    assert host.n_grants == P - 1 == host.n_certs
+
+
+# 7. wire offsets past 4 GiB -------------------------------------------------------------------------
+def test_offsets_past_4_gib(ver):
+    """Thirty-two bodies in the last 64 KiB of a wire of 2^32 + 64 KiB bytes: every offset the
+    decoder emits is the low-offset decode's plus the displacement, the signatures its."""
+    import torch
+
+    size = (1 << 32) + (64 << 10)
+    free, _ = torch.cuda.mem_get_info(torch.device("cuda", 0))
+    if free < size + (512 << 20):
+        pytest.skip(f"{free >> 20} MiB of device memory free, the test wants {(size >> 20) + 512}")
+    cases = DM.far_cases()
+    low = DM.batch(cases, per_req=3, mod=16)
+    n = low.wire.size
+    D = (size - n) // 16 * 16
+    assert n <= 64 << 10 and D + int(low.resp_off.min()) >= 1 << 32
+    assert {(int(o) + D) % 16 for o in low.resp_off} == set(range(16))
+    host = mh.write1_reply_decode(low, DM.IDS)
+    N, C = host.n_grants, host.n_certs
+    want = {k: v.copy() for k, v in host.trimmed().items()}
+    for k in ("grant_off", "cert_key_off", "cert_val_off"):
+        want[k] += np.uint64(D)
+    decoded = np.isin(low.resp_kind, [mh.W1_OK, mh.W1_REFUSED]) & np.isin(want["resp_status"], [mh.W1R_OK, mh.W1R_UNKNOWN_SERVER])
+    want["resp_client_off"][decoded] += np.uint64(D)  # an undecoded response keeps 0 / 0
+    assert decoded.any() and not decoded.all() and (want["resp_client_off"][~decoded] == 0).all()
+    assert N > 16 and C > 64 and {s % 16 for s in DM.sig_sources(low, host.trimmed())} == set(range(16))
+    small = mh.DeviceWrite1Replies(low, 0)
+    big = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+    big[D:D + n] = small.wire
+    dr = mh.DeviceWrite1Replies.from_tensors(
+        low.n_resps, low.n_reqs, low.n_ops, wire=big, resp_off=small.resp_off + D, resp_len=small.resp_len,
+        resp_kind=small.resp_kind, req_resp_off=small.req_resp_off, strings=small.strings, req_op_off=small.req_op_off,
+        op_key_off=small.op_key_off, op_key_len=small.op_key_len)
+    got = _decode_device(ver, None, N + 3, C + 3, dr=dr)
+    del big, dr
+    _assert_decoded(got, want, N, C)
+    t = got.trimmed()
+    for k in ("grant_off", "cert_key_off", "cert_val_off"):
+        assert (t[k] >= 1 << 32).all(), k
+    assert (t["resp_client_off"][decoded] >= 1 << 32).all()
+    np.testing.assert_array_equal(t["sig"], host.trimmed()["sig"])
+
+
+# 8. request grouping, the wire's end ------------------------------------------------------------------
+def test_request_grouping_device_equals_host(ver):
+    _device_equals_host(ver, DM.grouping_batch(), DM.IDS, model=True)
+
+
+@pytest.mark.parametrize("residue", range(16))
+def test_signature_ends_the_wire(ver, residue):
+    """The last response ends on the wire's last byte and its signature is its last field:
+    the gather's last chunk ends the buffer, the source at each position in a chunk."""
+    by = {c.name: c for c in DM.corpus()}
+    last = DM.Case("sig_last", DM.reply(DM.multigrant([(DM.K1, DM.grant(DM.K1, 11))])), (DM.K1,))
+    cases = (by["rep:sigs"], by["mutate:2"], last)
+    n0 = DM.batch(cases, per_req=2, lead=0, tail=0).wire.size
+    r = DM.batch(cases, per_req=2, lead=(residue - (n0 - 256)) % 16, tail=0)
+    assert int(r.resp_off[-1]) + int(r.resp_len[-1]) == r.wire.size and (r.wire.size - 256) % 16 == residue
+    host = _device_equals_host(ver, r, DM.IDS, model=True)
+    assert host.arrays["grant_flags"][-1] == mh.W1G_HAS_SIG
+    np.testing.assert_array_equal(host.arrays["sig"][-1], r.wire[-256:])
+
+
+# 9. scratch that grows between calls on two streams ------------------------------------------------------
+@pytest.mark.parametrize("order", ["small_large_small", "large_small_large"])
+def test_scratch_growth_across_streams(pems, order):
+    """A fresh context; three calls alternating between two streams with nothing between them
+    but what a call itself waits for; the second call's batch needs other scratch sizes
+    than the first's.  Each call has guard-filled outputs of its own."""
+    import torch
+
+    small = DM.batch(tuple(c for c in DM.corpus() if c.name.startswith("mutate:"))[:8])
+    large = DM.batch(DM.pattern_cases(300), per_req=3)
+    seq = [small, large, small] if order == "small_large_small" else [large, small, large]
+    hosts = [mh.write1_reply_decode(r, DM.IDS) for r in seq]
+    assert hosts[0].n_grants > 0 and hosts[1].n_grants > 0
+    drs = [mh.DeviceWrite1Replies(r, 0) for r in seq]
+    outs = [mh.DeviceWrite1Decoded(r.n_resps, h.n_grants + 3, h.n_certs + 3, fill=FILL) for r, h in zip(seq, hosts)]
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    v = mh.Verifier([mh.pem_modulus(p) for p in pems], 0)
+    v.set_server_ids(DM.IDS)
+    torch.cuda.synchronize()
+    rcs = [v.write1_reply_decode_device(dr, o, stream=s.cuda_stream) for dr, o, s in zip(drs, outs, (a, b, a))]
+    torch.cuda.synchronize()
+    v.close()
+    for rc, o, h in zip(rcs, outs, hosts):
+        _assert_decoded(o.to_host(rc), h.trimmed(), h.n_grants, h.n_certs)

@@ -600,22 +600,24 @@ def corpus() -> Tuple[Case, ...]:
     return tuple(out)
 
 
-def batch(cases, layout: str = "packed", per_req: int = 4) -> mh.Write1Replies:
+def batch(cases, layout: str = "packed", per_req: int = 4, lead: int = 5, tail: int = 3, mod: int = 0) -> mh.Write1Replies:
     """The cases as one batch: `per_req` consecutive responses share a request, whose ops
     are the FIRST case's keys.  Layouts: packed (pad residues 0..3, any alignment),
-    shared (equal bodies point at one copy: aliased slices)."""
+    shared (equal bodies point at one copy: aliased slices).  `lead` / `tail` filler
+    bytes before the first and after the last body (tail=0: the last body ends the wire);
+    mod > 0: body i begins at an offset congruent to i modulo `mod` instead."""
     P = len(cases)
-    parts, pos, off, at = [b"\xee" * 5], 5, [], {}
+    parts, pos, off, at = [b"\xee" * lead], lead, [], {}
     for i, c in enumerate(cases):
         if layout == "shared" and c.body in at:
             off.append(at[c.body])
             continue
-        pad = i % 4
+        pad = (i - pos) % mod if mod else i % 4
         parts += [b"\xee" * pad, c.body]
         at[c.body] = pos + pad
         off.append(pos + pad)
         pos += pad + len(c.body)
-    parts.append(b"\xee" * 3)
+    parts.append(b"\xee" * tail)
     heads = list(range(0, P, per_req))
     keys = [cases[h].keys for h in heads]
     flat = [k for ks in keys for k in ks]
@@ -642,6 +644,181 @@ def replies_of(case) -> mh.Write1Replies:
                             resp_kind=np.array([KIND_OF[int(k)] for k in issued.req_kind], np.uint8),
                             req_resp_off=np.arange(Q + 1, dtype=np.uint32), strings=batch.strings,
                             req_op_off=batch.req_op_off, op_key_off=batch.op_key_off, op_key_len=batch.op_key_len)
+
+
+# ---------------------------------------------------------------------------
+# Bodies and batches for the launch edges of the device form
+# ---------------------------------------------------------------------------
+K1, K2 = b"alpha", b"beta"
+BAD_CERT_VALUE = b"\x0a\x05ab"  # a WriteCertificate whose one entry runs past its end
+
+
+def heavy(n: int = MAX_ENTRIES, bad=None, fb: bool = False, light: bool = False, sig: bool = True) -> bytes:
+    """A body of 1 + n level-2 entries: one MultiGrant (one grant, its signature unless
+    `sig` is off) and n currentCertificates entries with distinct keys, each value
+    writecert([K1], 1).  The entries listed in `bad` (an index or several) hold a Grant
+    that runs past its end: MALFORMED, which only that entry's level-2 lane finds.  `fb`
+    appends an unknown field to the grant: FALLBACK, which only the MultiGrant lane finds.
+    `light`: empty certificate values (a large batch stays small in bytes)."""
+    bad = () if bad is None else (bad,) if isinstance(bad, int) else tuple(bad)
+    assert all(0 <= j < n for j in bad) and not (light and bad)
+    g = grant(K1, 11) + (b"\x48\x01" if fb else b"")
+    certs = [(b"h%02d" % j, b"" if light else writecert([K1], 1, bad_grant=j in bad)) for j in range(n)]
+    return reply(multigrant([(K1, g)], sigs=None if sig else []), certs)
+
+
+def level2_entries(body: bytes, kind: int = mh.W1_OK) -> int:
+    """How many level-2 entries a response has: 1 + its currentCertificates entries on the
+    wire when its kind is parsed and its top level is accepted (it parses, map keys and
+    strings included, and holds at most one multiGrant, at most MAX_ENTRIES certificate
+    entries and no entry with two values); 0 otherwise.  Read off the field tree."""
+    if kind not in (mh.W1_OK, mh.W1_REFUSED):
+        return 0
+    try:
+        n_mg, ces = 0, []
+        for f, wt, v, o, l in _msg(body, 0, len(body)):
+            if wt != 2:
+                continue
+            if f == 1:
+                n_mg += 1
+            elif f == 2:
+                ces.append(parse_entry(body, o, l))
+            elif f in (3, 4):
+                _utf8(body, o, l)
+    except Malformed:
+        return 0
+    if n_mg > 1 or len(ces) > MAX_ENTRIES or any(e.n_val > 1 for e in ces):
+        return 0
+    return 1 + len(ces)
+
+
+def n_level2_entries(r: mh.Write1Replies) -> int:
+    """level2_entries summed over a batch (each distinct slice and kind parsed once)."""
+    wire = np.asarray(r.wire, np.uint8).tobytes()
+    trip, counts = np.unique(np.stack([np.asarray(r.resp_off, np.uint64), np.asarray(r.resp_len, np.uint64),
+                                       np.asarray(r.resp_kind, np.uint64)], 1), axis=0, return_counts=True)
+    return sum(int(n) * level2_entries(wire[int(o):int(o) + int(l)], int(k)) for (o, l, k), n in zip(trip, counts))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_cases() -> Dict[str, Case]:
+    """The heavy bodies by name, with the unparsed kinds and the level-1 rejects the
+    level-2 pattern mixes them with."""
+    two_mg = heavy(8) + RM.ld(0x0A, multigrant([(K2, grant(K2, 12))], sigs=[]))  # merged by the parser: the whole body at level 1
+    cs = [Case("ok:heavy", heavy(), (K1, K2)),
+          Case("ok:heavy_light", heavy(light=True), (K2, K1)),
+          Case("ok:heavy_no_sig", heavy(5, sig=False), (K1,)),
+          Case("mal:heavy_bad_63", heavy(bad=63), (K1, K2)),
+          Case("mal:heavy_bad_0_and_63", heavy(bad=(0, 63)), (K1, K2)),
+          Case("mal:heavy_bad_31_and_32", heavy(bad=(31, 32)), (K1, K2)),
+          Case("fb:heavy", heavy(fb=True), (K1, K2)),
+          Case("mal:heavy_fb_and_bad_0", heavy(fb=True, bad=0), (K1, K2)),
+          Case("mal:level1_one_byte", b"\x0a", (K1, K2)),
+          Case("fb:level1_two_multigrants", two_mg, (K1, K2)),
+          Case("kind:failed", b"\xff\xff", (K1, K2), mh.W1_REQUEST_FAILED),
+          Case("kind:other_heavy_bad", heavy(bad=63), (K1, K2), mh.W1_OTHER)]
+    return {c.name: c for c in cs}
+
+
+# twelve responses: level-2 entries exist only at 2, 6, 7, 8 and 10, so the entry offsets
+# repeat (a run of responses without entries) at the start, in the middle and at the end
+PATTERN = ("kind:failed", "mal:level1_one_byte", "ok:heavy", "kind:other_heavy_bad", "kind:failed", "kind:other_heavy_bad",
+           "mal:heavy_bad_63", "fb:heavy", "mal:heavy_fb_and_bad_0", "fb:level1_two_multigrants", "mal:heavy_bad_0_and_63",
+           "kind:failed")
+
+
+def pattern_cases(P: int) -> Tuple[Case, ...]:
+    """The first P responses of PATTERN repeated."""
+    ec = edge_cases()
+    return tuple(ec[PATTERN[i % len(PATTERN)]] for i in range(P))
+
+
+def batch_explicit(bodies, which, kinds, req_resp_off, req_keys, lead: int = 5, tail: int = 3) -> mh.Write1Replies:
+    """A batch from its parts: response p is bodies[which[p]] (each body once in the wire,
+    pad residues 0..3: responses alias), of kind kinds[p]; the requests are the CSR
+    req_resp_off, request q's ops the keys req_keys[q]."""
+    parts, pos, at = [b"\xee" * lead], lead, []
+    for i, b in enumerate(bodies):
+        parts += [b"\xee" * (i % 4), b]
+        at.append(pos + i % 4)
+        pos += i % 4 + len(b)
+    parts.append(b"\xee" * tail)
+    which = np.asarray(which, np.int64)
+    flat = [k for ks in req_keys for k in ks]
+    strings, k_off, k_len = RM.pack(list(flat), lambda i: i % 3)
+    assert len(req_keys) == len(req_resp_off) - 1 and int(req_resp_off[-1]) == which.size
+    return mh.Write1Replies(
+        wire=np.frombuffer(b"".join(parts), np.uint8).copy(), resp_off=np.array(at, np.uint64)[which],
+        resp_len=np.array([len(b) for b in bodies], np.uint32)[which], resp_kind=np.asarray(kinds, np.uint8),
+        req_resp_off=np.asarray(req_resp_off, np.uint32), strings=strings,
+        req_op_off=np.concatenate([[0], np.cumsum([len(k) for k in req_keys])]).astype(np.uint32),
+        op_key_off=k_off if flat else np.zeros(0, np.uint64), op_key_len=k_len if flat else np.zeros(0, np.uint32))
+
+
+def cap_batch(P: int, last: bytes) -> mh.Write1Replies:
+    """P responses of two level-2 entries each (one grant without signature, one
+    certificate entry with an empty value), all slices of one copy; the last response
+    alone is `last`.  Five requests of unequal size."""
+    small = reply(multigrant([(K1, grant(K1, 11))], sigs=[]), [(K1, b"")])
+    which = np.zeros(P, np.int64)
+    which[-1] = 1
+    cuts = [0, 1, P // 3, P // 3 + 7, P - 2, P]
+    return batch_explicit([small, last], which, np.full(P, mh.W1_OK, np.uint8), cuts, [(K1,), (K2, K1), (), (K2,), (K1, K2)])
+
+
+SMALL_BAD = reply(multigrant([(K1, grant(K1, 11))], sigs=[]), [(K1, BAD_CERT_VALUE)])  # two entries, the second MALFORMED
+
+
+def grouping_batch() -> mh.Write1Replies:
+    """Requests without responses first, twice in a row in the middle and last; a request
+    without ops; a request of MOCHI_MAX_OPS_PER_CERT ops that name the replies' grants at
+    slots 0 and 63 alone, slot 0's key again at slot 7 (the first slot wins)."""
+    A, B = b"key-A", b"key-B"
+    bodies = [reply(multigrant([(K1, grant(K1, 11))]), [(K1, writecert([K1]))]),
+              reply(multigrant([(A, grant(A, 21)), (B, grant(B, 22))], IDS[1])),
+              reply(multigrant([(b"nobody", grant(b"nobody", 23)), (B, grant(B, 24))], IDS[2]), [(A, writecert([A], 1))])]
+    ops64 = [b"f%02d" % j for j in range(mh.MAX_OPS_PER_CERT)]
+    ops64[0], ops64[7], ops64[63] = A, A, B
+    reqs = [((), (K1,)),  # (responses, ops)
+            ((0, 1), (K1, K2)),
+            ((), ()),
+            ((), (b"x",)),
+            ((1, 0, 2), ()),
+            ((1, 2, 1), tuple(ops64)),
+            ((0,), (K2, K1)),
+            ((), (K1,))]
+    which = [w for ws, _ in reqs for w in ws]
+    return batch_explicit(bodies, which, np.full(len(which), mh.W1_OK, np.uint8),
+                          np.concatenate([[0], np.cumsum([len(ws) for ws, _ in reqs])]), [ks for _, ks in reqs])
+
+
+def far_cases() -> Tuple[Case, ...]:
+    """Thirty-two responses for the offsets past 4 GiB: with and without signature, with a
+    client id, with certificates, MALFORMED, FALLBACK, an unknown server, unparsed kinds."""
+    by = {c.name: c for c in corpus()}
+    ec = edge_cases()
+    names = ["mutate:0", "mutate:2", "mutate:4", "rep:certs", "rep:sigs", "rep:scalars", "sig:255", "ok:sig_value_twice",
+             "sig:256", "sid:unknown", "mal:nested_cert_grant", "fb:grant_unknown_field", "kind:request_failed",
+             "kind:other", "kind:refused", "key:differs", "utf8:key_multibyte_ok", "ok:64_certs", "mg:absent"]
+    cs = [by[n] for n in names] + [ec[n] for n in ("ok:heavy_light", "mal:heavy_bad_63", "ok:heavy_no_sig", "fb:heavy")]
+    cs += [c for c in corpus() if c.name in ("mutate:1", "mutate:3", "mutate:5", "mutate:6", "mutate:9")][:9]
+    return tuple(cs[:32])
+
+
+def sig_sources(r: mh.Write1Replies, d: dict) -> List[int]:
+    """Wire offset of every decoded signature (grants with W1G_HAS_SIG), found inside its
+    response's slice; a signature whose bytes occur there more than once is left out."""
+    wire = np.asarray(r.wire, np.uint8).tobytes()
+    out = []
+    for p in range(r.n_resps):
+        body = wire[int(r.resp_off[p]):int(r.resp_off[p]) + int(r.resp_len[p])]
+        for g in range(int(d["resp_grant_off"][p]), int(d["resp_grant_off"][p + 1])):
+            if int(d["grant_flags"][g]) & mh.W1G_HAS_SIG:
+                s = d["sig"][g].tobytes()
+                assert s in body
+                if body.count(s) == 1:
+                    out.append(int(r.resp_off[p]) + body.find(s))
+    return out
 
 
 def assert_equal(got: dict, want: dict, what: str = "") -> None:
