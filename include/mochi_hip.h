@@ -986,6 +986,152 @@ int mochi_write1_reply_decode_device(mochi_ctx* ctx, const mochi_write1_replies*
 int mochi_ctx_read_w1_decode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n_kernels);
 
 /* ------------------------------------------------------------------------
+ * Write1 REQUEST DECODE: the server's side of the Write1 round.  The
+ * Write1ToServer bodies a server received (field 107 of a ProtocolMessage,
+ * MochiProtocol.proto:92-97) become the wire half of mochi_write1_batch, with
+ * protobuf-java 3.16.3 parsing semantics (as the reply decoder: singular
+ * fields last-wins, unknown fields and known field numbers with a foreign wire
+ * type skipped, groups to depth 100, field number 0 or a bad varint malformed,
+ * every string strict UTF-8 -- clientId, transactionHash and operand1 / 2 / 3
+ * of every Operation whatever its action --, seed and Operation.action the low
+ * 32 bits of their varint).  The bytes are a Byzantine client's: every read
+ * stays inside the request's slice.
+ *
+ *   Write1ToServer = [0A clientId] [12 Transaction] [18 seed] [22 transactionHash]
+ *   Transaction    = { 0A Operation }
+ *   Operation      = [08 action] [12 operand1] [1A operand2] [22 operand3]
+ *
+ * Input.  Request q is wire[msg_off[q], +msg_len[q]) (any alignment; slices
+ * may alias).  n_reqs is at most 2^24.
+ * ------------------------------------------------------------------------ */
+typedef struct mochi_write1_requests {
+  uint32_t n_reqs, _pad0;        /* Q */
+  const uint8_t*  wire;    uint64_t wire_len;
+  const uint64_t* msg_off;       /* [Q] */
+  const uint32_t* msg_len;       /* [Q] */
+} mochi_write1_requests;
+
+/* Per-request decode status. */
+enum mochi_w1q_status {
+  MOCHI_W1Q_OK = 0,
+  /* protobuf-java would throw while parsing the body as a Write1ToServer */
+  MOCHI_W1Q_MALFORMED = 1,
+  /* well-formed (validated whole, never malformed) but not decoded:
+   * `transaction` given more than once (a merge); more than
+   * MOCHI_MAX_OPS_PER_CERT operations */
+  MOCHI_W1Q_FALLBACK = 2,
+};
+
+/* Output; every array is the caller's.  Offsets point into `wire` (zero copy);
+ * a field that is absent gives the request's own offset and length 0.  A
+ * request whose status is not OK has no ops, seed 0 and slices 0 / 0: the
+ * caller sends it no reply.
+ *   req_seed: Write1ToServer.seed.  req_hash_*: transactionHash.
+ *   req_client_*: clientId.  req_op_off [Q+1]: a CSR over the ops.
+ * Per op, in transaction order: op_key_off / op_key_len = operand1; op_flags =
+ * MOCHI_W1OP_WRITE for action 2, MOCHI_W1OP_DELETE for action 1 and 0 for any
+ * other value (unknown enum values included); op_obj = the index of the op's
+ * key among the batch's distinct keys, MOCHI_W1_NONE for an op that has none.
+ * Keys are compared byte for byte; only WRITE and DELETE ops with a non-empty
+ * operand1 take part (every op here belongs to an OK request); keys are
+ * numbered by their first op in op order, so the host and device forms give
+ * identical arrays.  key_op[u] = the first op that holds key u (the slice to
+ * look the store up with).
+ *
+ * These arrays are mochi_write1_batch's strings (= wire), req_op_off,
+ * req_seed, req_hash_*, op_key_* and op_obj, and the wire half of op_flags
+ * (mochi_write1_state_join adds the rest); with ids = wire they are
+ * mochi_write1_reply_source.req_client_* too.
+ *
+ * Capacity: op_cap is the entries the per-op arrays and key_op hold.  n_ops (a
+ * host field in both forms) is always written, and so are the per-request
+ * arrays and req_op_off; when op_cap < n_ops the call returns MOCHI_EINVAL and
+ * touches no per-op array, key_op or n_keys. */
+typedef struct mochi_write1_requests_decoded {
+  uint8_t*  req_status;       /* [Q] enum mochi_w1q_status */
+  uint32_t* req_seed;         /* [Q] */
+  uint64_t* req_hash_off;     /* [Q] */
+  uint32_t* req_hash_len;     /* [Q] */
+  uint64_t* req_client_off;   /* [Q] */
+  uint32_t* req_client_len;   /* [Q] */
+  uint32_t* req_op_off;       /* [Q+1] */
+  uint32_t  n_ops;            /* out */
+  uint32_t  n_keys;           /* out (host form; the device form leaves it 0) */
+  uint32_t  op_cap, _pad0;    /* in  */
+  uint64_t* op_key_off;       /* [O] */
+  uint32_t* op_key_len;       /* [O] */
+  uint8_t*  op_flags;         /* [O] */
+  uint32_t* op_obj;           /* [O] */
+  uint32_t* key_op;           /* [op_cap]; n_keys entries written */
+} mochi_write1_requests_decoded;
+
+/* A safe op_cap from wire_len and n_reqs alone: slices may alias, so every
+ * request is taken at the whole blob; an op takes two bytes or more and a
+ * decoded request holds at most MOCHI_MAX_OPS_PER_CERT.  Safe, not tight. */
+uint64_t mochi_write1_request_decode_bound(uint64_t wire_len, uint32_t n_reqs);
+
+/* Host form: every array in host memory, no signer, no GPU.  MOCHI_EINVAL for
+ * a request slice outside `wire` or more than 2^24 requests. */
+int mochi_write1_request_decode(const mochi_write1_requests* requests, mochi_write1_requests_decoded* out);
+
+/* Device form: every array of `requests` and `out` and n_keys_dev (one
+ * uint32_t) in DEVICE memory, the structs themselves on the host.  Scratch
+ * hangs off the signer (its own, apart from the issue and reply encode
+ * calls'); the call takes the signer's lock and orders itself behind the
+ * signer's last call on another stream as mochi_write1_reply_encode_device
+ * does.  It waits once, for n_ops, applies the capacity rule on the host and
+ * returns with the remaining kernels enqueued on `stream` (hipStream_t; NULL =
+ * null stream); the number of distinct keys goes to *n_keys_dev.  Same arrays
+ * as the host form; the caller's offsets are trusted, the bytes of `wire` are
+ * not. */
+int mochi_write1_request_decode_device(mochi_signer* s, const mochi_write1_requests* requests,
+                                       mochi_write1_requests_decoded* out, uint32_t* n_keys_dev, void* stream);
+/* Per-kernel device time (ms) of the last mochi_write1_request_decode_device
+ * call made while profiling was on (mochi_signer_set_profiling) and that
+ * emitted: [0] k_w1q_req, [1] the entry scan, [2] k_w1q_ops, [3] k_w1q_final +
+ * the op scan + k_w1q_offsets, [4] k_w1q_emit, [5] the table clear +
+ * k_w1q_claim, [6] k_w1q_rank, [7] the key scan, [8] k_w1q_number.  Waits for
+ * that call.  n <= 9. */
+int mochi_signer_read_request_profile(mochi_signer* s, float* kernel_ms, uint32_t n);
+
+/* STATE JOIN: from "state per distinct key" to the per-op state arrays of
+ * mochi_write1_batch.  The host looks the store up once per distinct key
+ * (key_op names an op that holds it) and gives, per key u: key_flags =
+ * MOCHI_W1OP_LOCAL | MOCHI_W1OP_HAS_SVOC as they apply; key_epoch = the
+ * container's current epoch; key_given_off [U+1], a CSR over the container's
+ * given Write1 grants, each with its timestamp given_ts and given_stored, its
+ * index among the batch's stored grants. */
+typedef struct mochi_write1_key_state {
+  uint32_t n_keys, n_given;      /* U, G */
+  const uint8_t*  key_flags;     /* [U] */
+  const int64_t*  key_epoch;     /* [U] */
+  const uint32_t* key_given_off; /* [U+1] */
+  const int64_t*  given_ts;      /* [G] */
+  const uint32_t* given_stored;  /* [G] */
+} mochi_write1_key_state;
+
+/* Per op o of request q with u = op_obj[o] != MOCHI_W1_NONE: op_flags[o] =
+ * op_flags_wire[o] | key_flags[u]; op_epoch[o] = key_epoch[u]; op_stored[o] =
+ * given_stored of the first entry of u's list whose timestamp equals
+ * key_epoch[u] + req_seed[q] (64-bit wrapping, seed unsigned), else
+ * MOCHI_W1_NONE (isGivenWrite1GrantsEmpty() || getGrantIfExistsAtTimeStamp(ts)
+ * == null, InMemoryDataStore.java:127-128).  An op without a key index keeps
+ * its flags and gets epoch 0 and MOCHI_W1_NONE.  op_flags may be
+ * op_flags_wire (in place).
+ * Host form: MOCHI_EINVAL for a req_op_off that is not a CSR over n_ops, a
+ * key_given_off that is not a CSR over n_given, or an op_obj >= n_keys. */
+int mochi_write1_state_join(uint32_t n_reqs, uint32_t n_ops, const uint32_t* req_op_off, const uint32_t* req_seed,
+                            const uint8_t* op_flags_wire, const uint32_t* op_obj, const mochi_write1_key_state* keys,
+                            uint8_t* op_flags, int64_t* op_epoch, uint32_t* op_stored);
+/* Device form: every array (those of `keys` too) in DEVICE memory; one kernel
+ * on `stream` on the signer's device, no host wait, no scratch; the inputs are
+ * trusted. */
+int mochi_write1_state_join_device(mochi_signer* s, uint32_t n_reqs, uint32_t n_ops, const uint32_t* req_op_off,
+                                   const uint32_t* req_seed, const uint8_t* op_flags_wire, const uint32_t* op_obj,
+                                   const mochi_write1_key_state* keys, uint8_t* op_flags, int64_t* op_epoch,
+                                   uint32_t* op_stored, void* stream);
+
+/* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps
  * (Write2ToServerRequestHandler.handle -> processWrite2ToServer on a 2..20
  * thread pool, MochiServer.java:36-40), coalesced across threads into one

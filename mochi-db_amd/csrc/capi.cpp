@@ -18,6 +18,7 @@
 #include "w1_decode.h"
 #include "w1_issue.h"
 #include "w1_reply.h"
+#include "w1_request.h"
 
 using namespace mochi;
 
@@ -1142,8 +1143,12 @@ struct mochi_signer {
   // Write1 reply encoder (w1_reply.hip): scratch of its own, so that it can run behind an
   // issue call whose kernels are still using w1.scratch
   EncState w1r;
+  // Write1 request decoder (w1_request.hip): the per-request scratch, its total is n_ops;
+  // the per-op scratch (claim table, key numbering) is sized once n_ops is known
+  EncState w1q;
+  DevBuf w1q_tab;
   hipEvent_t ev_tot = nullptr;  // totals landed
-  ScratchOrder order;           // one for both encoders
+  ScratchOrder order;           // one for the encoders and the request decoder
   bool profiling = false;
 };
 
@@ -1619,6 +1624,139 @@ int mochi_signer_read_reply_profile(mochi_signer* s, float* kernel_ms, uint32_t 
   static const int kSpan[mochi::kW1ReplyStages][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
   return s->w1r.read_profile(kSpan, mochi::kW1ReplyStages, kernel_ms, n,
                              "no reply encode call was made while profiling was on");
+}
+
+}  // extern "C"
+
+// ---- Write1 request decoder and key-state join (w1_request.hip / w1_request_host.cpp) ----
+namespace {
+
+int check_write1_requests(const mochi_write1_requests* r, const mochi_write1_requests_decoded* o) {
+  if (!r || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (!o->req_op_off) return fail(MOCHI_EINVAL, "req_op_off required");
+  if (r->n_reqs && (!r->msg_off || !r->msg_len || (!r->wire && r->wire_len)))
+    return fail(MOCHI_EINVAL, "wire / msg_off / msg_len required");
+  if (r->n_reqs && (!o->req_status || !o->req_seed || !o->req_hash_off || !o->req_hash_len || !o->req_client_off ||
+                    !o->req_client_len))
+    return fail(MOCHI_EINVAL, "the per-request outputs are required");
+  if (r->n_reqs > mochi::w1q::kMaxReqs) return fail(MOCHI_EINVAL, "more than 2^24 requests");
+  if (o->op_cap && (!o->op_key_off || !o->op_key_len || !o->op_flags || !o->op_obj || !o->key_op))
+    return fail(MOCHI_EINVAL, "the per-op outputs and key_op are required (op_cap > 0)");
+  return MOCHI_OK;
+}
+
+int w1q_capacity_error(const mochi_write1_requests_decoded* o) {
+  return capacity_error("op_cap", o->op_cap, "decoded ops", o->n_ops);
+}
+
+int run_write1_request_device(mochi_signer* s, const mochi_write1_requests* r, mochi_write1_requests_decoded* o,
+                              uint32_t* n_keys_dev, hipStream_t st) {
+  const uint32_t Q = r->n_reqs;
+  EncState& x = s->w1q;
+  o->n_ops = o->n_keys = 0;
+  mochi::W1ReqArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.in = *r;
+  a.v.out = *o;
+  a.Q = Q;
+  a.n_keys = n_keys_dev;
+  int rc = x.begin(a, mochi::w1q_layout, Q + 1, 8, s->profiling, mochi::kW1ReqEvents);
+  if (rc) return rc;
+  // one scratch per signer: a call on another stream waits for the last call's kernels
+  HIP_TRY(s->order.acquire(st));
+  HIP_TRY(mochi::launch_w1q_count(a, st));
+  if ((rc = x.fetch_totals(a.off64 + Q, 8, s->ev_tot, st))) return rc;
+  const uint64_t tot = *(const uint64_t*)x.tot.p;
+  o->n_ops = a.n_ops = (uint32_t)tot;
+  const bool fits = o->n_ops <= o->op_cap;
+  if (fits) {
+    a.slots = (uint32_t)mochi::w1_table_slots(a.n_ops);
+    size_t scan_bytes = 0;
+    HIP_TRY(mochi::enc_scan_temp_bytes(a.n_ops + 1, &scan_bytes));
+    if ((rc = s->w1q_tab.ensure(mochi::w1q_table_layout(a, nullptr))) || (rc = x.scan.ensure(scan_bytes))) return rc;
+    mochi::w1q_table_layout(a, s->w1q_tab.p);
+    a.scan_temp = x.scan.p;
+    a.scan_temp_bytes = x.scan.cap;
+    HIP_TRY(mochi::launch_w1q_emit(a, st));
+  }
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(s->order.release(st));
+  return fits ? MOCHI_OK : w1q_capacity_error(o);
+}
+
+int check_write1_join(uint32_t n_ops, const uint32_t* req_op_off, const uint32_t* req_seed, const uint8_t* op_flags_wire,
+                      const uint32_t* op_obj, const mochi_write1_key_state* k, const uint8_t* op_flags,
+                      const int64_t* op_epoch, const uint32_t* op_stored) {
+  if (!k || !req_op_off) return fail(MOCHI_EINVAL, "null argument");
+  if (n_ops && (!req_seed || !op_flags_wire || !op_obj || !op_flags || !op_epoch || !op_stored))
+    return fail(MOCHI_EINVAL, "an op array or req_seed is missing");
+  if (!k->key_given_off || (k->n_keys && (!k->key_flags || !k->key_epoch)) ||
+      (k->n_given && (!k->given_ts || !k->given_stored)))
+    return fail(MOCHI_EINVAL, "a key state array is missing");
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mochi_write1_request_decode_bound(uint64_t wire_len, uint32_t n_reqs) {
+  const uint64_t per = wire_len / 2 < mochi::w1q::kMaxOps ? wire_len / 2 : mochi::w1q::kMaxOps;
+  return per * n_reqs;
+}
+
+int mochi_write1_request_decode(const mochi_write1_requests* r, mochi_write1_requests_decoded* o) {
+  int rc = check_write1_requests(r, o);
+  if (rc) return rc;
+  const char* err = nullptr;
+  rc = mochi_host::write1_request_decode(r, o, &err);
+  if (rc && err) return fail(rc, "mochi_write1_request_decode: %s", err);
+  return rc ? w1q_capacity_error(o) : MOCHI_OK;
+}
+
+int mochi_write1_request_decode_device(mochi_signer* s, const mochi_write1_requests* r, mochi_write1_requests_decoded* o,
+                                       uint32_t* n_keys_dev, void* stream) {
+  if (!s) return fail(MOCHI_EINVAL, "null signer");
+  if (!n_keys_dev) return fail(MOCHI_EINVAL, "n_keys_dev required");
+  int rc = check_write1_requests(r, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(s->mu);
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  return run_write1_request_device(s, r, o, n_keys_dev, (hipStream_t)stream);
+}
+
+int mochi_signer_read_request_profile(mochi_signer* s, float* kernel_ms, uint32_t n) {
+  if (!s || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(s->mu);
+  static const int kSpan[mochi::kW1ReqStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}};
+  return s->w1q.read_profile(kSpan, mochi::kW1ReqStages, kernel_ms, n,
+                             "no request decode call was made while profiling was on");
+}
+
+int mochi_write1_state_join(uint32_t n_reqs, uint32_t n_ops, const uint32_t* req_op_off, const uint32_t* req_seed,
+                            const uint8_t* op_flags_wire, const uint32_t* op_obj, const mochi_write1_key_state* keys,
+                            uint8_t* op_flags, int64_t* op_epoch, uint32_t* op_stored) {
+  int rc = check_write1_join(n_ops, req_op_off, req_seed, op_flags_wire, op_obj, keys, op_flags, op_epoch, op_stored);
+  if (rc) return rc;
+  const mochi::w1q::JoinArgs a{n_reqs, n_ops, req_op_off, req_seed, op_flags_wire, op_obj, *keys, op_flags, op_epoch, op_stored};
+  const char* err = nullptr;
+  rc = mochi_host::write1_state_join(&a, &err);
+  return rc ? fail(rc, "mochi_write1_state_join: %s", err) : MOCHI_OK;
+}
+
+int mochi_write1_state_join_device(mochi_signer* s, uint32_t n_reqs, uint32_t n_ops, const uint32_t* req_op_off,
+                                   const uint32_t* req_seed, const uint8_t* op_flags_wire, const uint32_t* op_obj,
+                                   const mochi_write1_key_state* keys, uint8_t* op_flags, int64_t* op_epoch,
+                                   uint32_t* op_stored, void* stream) {
+  if (!s) return fail(MOCHI_EINVAL, "null signer");
+  int rc = check_write1_join(n_ops, req_op_off, req_seed, op_flags_wire, op_obj, keys, op_flags, op_epoch, op_stored);
+  if (rc) return rc;
+  DeviceGuard dev(s->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
+  const mochi::w1q::JoinArgs a{n_reqs, n_ops, req_op_off, req_seed, op_flags_wire, op_obj, *keys, op_flags, op_epoch, op_stored};
+  HIP_TRY(mochi::launch_w1q_join(a, (hipStream_t)stream));
+  return MOCHI_OK;
 }
 
 }  // extern "C"

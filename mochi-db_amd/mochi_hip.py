@@ -210,6 +210,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_write1_reply_decode.argtypes = [vp, vp, vp, u32, vp]
     lib.mochi_write1_reply_decode_device.argtypes = [vp, vp, vp, vp]
     lib.mochi_ctx_read_w1_decode_profile.argtypes = [vp, vp, u32]
+    lib.mochi_write1_request_decode_bound.restype = u64
+    lib.mochi_write1_request_decode_bound.argtypes = [u64, u32]
+    lib.mochi_write1_request_decode.argtypes = [vp, vp]
+    lib.mochi_write1_request_decode_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mochi_signer_read_request_profile.argtypes = [vp, vp, u32]
+    lib.mochi_write1_state_join.argtypes = [u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mochi_write1_state_join_device.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -1456,6 +1463,38 @@ class DeviceSigner:
             raise MochiError(f"mochi_signer_read_reply_profile: {_err(self.lib)}")
         return dict(zip(W1_REPLY_STAGES, (float(x) for x in ms)))
 
+    def request_decode_device(self, dreqs: "DeviceWrite1Requests", out: "DeviceWrite1RequestsDecoded", stream: int = 0,
+                              check: bool = True) -> int:
+        """mochi_write1_request_decode_device: Write1ToServer bodies in device memory to
+        the wire half of a Write1 batch with its key numbering, in device memory.  Sets
+        out.n_ops (the key count goes to the device word out.n_keys_dev); returns the rc,
+        EINVAL when out.op_cap is too small (raises then if `check`)."""
+        r, o = dreqs.to_c(), out.to_c()
+        rc = self.lib.mochi_write1_request_decode_device(self.h, ctypes.addressof(r), ctypes.addressof(o),
+                                                         out.n_keys_dev.data_ptr(), stream)
+        out.n_ops = int(o.n_ops)
+        short = rc == EINVAL and out.n_ops > out.op_cap
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_write1_request_decode_device rc={rc}: {_err(self.lib)}")
+        return rc
+
+    def read_request_profile(self) -> dict:
+        """Per-kernel device ms of the last request_decode_device call made while profiling was on."""
+        ms = (ctypes.c_float * len(W1_REQUEST_STAGES))()
+        if self.lib.mochi_signer_read_request_profile(self.h, ms, len(W1_REQUEST_STAGES)) != OK:
+            raise MochiError(f"mochi_signer_read_request_profile: {_err(self.lib)}")
+        return dict(zip(W1_REQUEST_STAGES, (float(x) for x in ms)))
+
+    def state_join_device(self, n_reqs: int, n_ops: int, req_op_off, req_seed, op_flags_wire, op_obj,
+                          dkeys: "DeviceWrite1KeyState", op_flags, op_epoch, op_stored, stream: int = 0) -> None:
+        """mochi_write1_state_join_device over device tensors (op_flags may be op_flags_wire)."""
+        k = dkeys.to_c()
+        rc = self.lib.mochi_write1_state_join_device(
+            self.h, n_reqs, n_ops, req_op_off.data_ptr(), req_seed.data_ptr(), op_flags_wire.data_ptr(),
+            op_obj.data_ptr(), ctypes.addressof(k), op_flags.data_ptr(), op_epoch.data_ptr(), op_stored.data_ptr(), stream)
+        if rc != OK:
+            raise MochiError(f"mochi_write1_state_join_device rc={rc}: {_err(self.lib)}")
+
     def close(self):
         if self.h:
             self.lib.mochi_signer_destroy(self.h)
@@ -2064,6 +2103,262 @@ class DeviceWrite1Decoded:
         if self.sig is not None:
             arr["sig"] = self.sig.cpu().numpy()[:self.grant_cap]
         return Write1Decoded(rc=rc, n_grants=self.n_grants, n_certs=self.n_certs, arrays=arr)
+
+
+# ---------------------------------------------------------------------------
+# Write1 request decode (the server's side of the round): Write1ToServer bodies ->
+# the wire half of a Write1Batch with its batch-wide key numbering; the key-state join
+# ---------------------------------------------------------------------------
+W1Q_OK, W1Q_MALFORMED, W1Q_FALLBACK = range(3)
+W1_REQUEST_STAGES = ("k_w1q_req", "entry_scan", "k_w1q_ops", "final_scan_offsets", "k_w1q_emit", "k_w1q_claim",
+                     "k_w1q_rank", "key_scan", "k_w1q_number")
+
+
+class Write1Requests_C(ctypes.Structure):
+    _fields_ = [("n_reqs", ctypes.c_uint32), ("_pad0", ctypes.c_uint32), ("wire", ctypes.c_void_p),
+                ("wire_len", ctypes.c_uint64), ("msg_off", ctypes.c_void_p), ("msg_len", ctypes.c_void_p)]
+
+
+class Write1RequestsDecoded_C(ctypes.Structure):
+    _fields_ = [("req_status", ctypes.c_void_p), ("req_seed", ctypes.c_void_p), ("req_hash_off", ctypes.c_void_p),
+                ("req_hash_len", ctypes.c_void_p), ("req_client_off", ctypes.c_void_p),
+                ("req_client_len", ctypes.c_void_p), ("req_op_off", ctypes.c_void_p),
+                ("n_ops", ctypes.c_uint32), ("n_keys", ctypes.c_uint32), ("op_cap", ctypes.c_uint32),
+                ("_pad0", ctypes.c_uint32), ("op_key_off", ctypes.c_void_p), ("op_key_len", ctypes.c_void_p),
+                ("op_flags", ctypes.c_void_p), ("op_obj", ctypes.c_void_p), ("key_op", ctypes.c_void_p)]
+
+
+class Write1KeyState_C(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_uint32), ("n_given", ctypes.c_uint32), ("key_flags", ctypes.c_void_p),
+                ("key_epoch", ctypes.c_void_p), ("key_given_off", ctypes.c_void_p), ("given_ts", ctypes.c_void_p),
+                ("given_stored", ctypes.c_void_p)]
+
+
+# output arrays by what they are indexed with: "Q" requests, "Q1" the CSR, "O" ops, "K" key_op (op_cap entries)
+_W1Q_OUT = dict(req_status=(np.uint8, "Q"), req_seed=(np.uint32, "Q"), req_hash_off=(np.uint64, "Q"),
+                req_hash_len=(np.uint32, "Q"), req_client_off=(np.uint64, "Q"), req_client_len=(np.uint32, "Q"),
+                req_op_off=(np.uint32, "Q1"), op_key_off=(np.uint64, "O"), op_key_len=(np.uint32, "O"),
+                op_flags=(np.uint8, "O"), op_obj=(np.uint32, "O"), key_op=(np.uint32, "K"))
+
+
+@dataclass
+class Write1Requests:
+    """The Write1ToServer bodies a server received (mochi_write1_requests, host arrays)."""
+
+    wire: np.ndarray  # uint8
+    msg_off: np.ndarray  # uint64 [Q]
+    msg_len: np.ndarray  # uint32 [Q]
+
+    DTYPES = dict(wire=np.uint8, msg_off=np.uint64, msg_len=np.uint32)
+
+    @property
+    def n_reqs(self) -> int:
+        return int(np.asarray(self.msg_off).shape[0])
+
+    def arrays(self) -> dict:
+        return {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write1Requests_C()
+        c.n_reqs, c.wire_len = self.n_reqs, int(arrs["wire"].size)
+        for k, a in arrs.items():
+            if a.size == 0:  # an empty array still gets a valid address
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+@dataclass
+class Write1RequestsDecoded:
+    """Outputs of write1_request_decode (mochi_write1_requests_decoded): the caller's buffers,
+    whole (n_ops / n_keys say how much of the per-op ones / of key_op is meant)."""
+
+    rc: int
+    n_ops: int
+    n_keys: int
+    arrays: dict  # name -> array, names as in mochi_write1_requests_decoded
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def trimmed(self) -> dict:
+        """Every array cut to its meaning (per-op ones and key_op to 0 unless rc is OK)."""
+        Q = self.arrays["req_status"].shape[0]
+        ok = self.rc == OK
+        n = dict(Q=Q, Q1=Q + 1, O=self.n_ops if ok else 0, K=self.n_keys if ok else 0)
+        return {k: self.arrays[k][:n[w]] for k, (dt, w) in _W1Q_OUT.items()}
+
+
+def write1_request_decode_bound(wire_len: int, n_reqs: int) -> int:
+    """mochi_write1_request_decode_bound: a safe op_cap."""
+    return int(load_library().mochi_write1_request_decode_bound(int(wire_len), int(n_reqs)))
+
+
+def write1_request_decode_into(reqs: "Write1Requests", op_cap: int, fill: int = 0) -> "Write1RequestsDecoded":
+    """mochi_write1_request_decode into buffers of the given capacity, prefilled with `fill`.
+    rc is EINVAL with n_ops = the count needed when it is too small (no per-op array
+    touched); any other failure raises."""
+    lib = load_library()
+    r, keep = reqs.to_c()
+    Q = reqs.n_reqs
+    n = dict(Q=Q, Q1=Q + 1, O=int(op_cap), K=int(op_cap))
+    arr = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _W1Q_OUT.items()}
+    o = Write1RequestsDecoded_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a) if a.size else None)
+    o.op_cap = int(op_cap)
+    rc = lib.mochi_write1_request_decode(ctypes.addressof(r), ctypes.addressof(o))
+    if rc != OK and not (rc == EINVAL and o.n_ops > op_cap):
+        raise MochiError(f"mochi_write1_request_decode rc={rc}: {_err(lib)}")
+    return Write1RequestsDecoded(rc=rc, n_ops=int(o.n_ops), n_keys=int(o.n_keys), arrays=arr)
+
+
+def write1_request_decode(reqs: "Write1Requests") -> "Write1RequestsDecoded":
+    """Host form of the Write1 request decoder: the count first, then into buffers of
+    exactly the size needed."""
+    first = write1_request_decode_into(reqs, 0)
+    if first.rc == OK:
+        return first
+    return write1_request_decode_into(reqs, first.n_ops)
+
+
+@dataclass
+class Write1KeyState:
+    """The store's state per distinct key of a decoded batch (mochi_write1_key_state, host arrays)."""
+
+    key_flags: np.ndarray  # uint8 [U] W1OP_LOCAL | W1OP_HAS_SVOC
+    key_epoch: np.ndarray  # int64 [U]
+    key_given_off: np.ndarray  # uint32 [U+1]
+    given_ts: np.ndarray  # int64 [G]
+    given_stored: np.ndarray  # uint32 [G]
+
+    DTYPES = dict(key_flags=np.uint8, key_epoch=np.int64, key_given_off=np.uint32, given_ts=np.int64,
+                  given_stored=np.uint32)
+
+    def arrays(self) -> dict:
+        return {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = Write1KeyState_C()
+        c.n_keys, c.n_given = int(arrs["key_flags"].size), int(arrs["given_ts"].size)
+        for k, a in arrs.items():
+            if a.size == 0:
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def write1_state_join(req_op_off, req_seed, op_flags_wire, op_obj, keys: "Write1KeyState"):
+    """mochi_write1_state_join: (op_flags, op_epoch, op_stored) of a decoded batch."""
+    lib = load_library()
+    off = np.ascontiguousarray(req_op_off, np.uint32)
+    seed = np.ascontiguousarray(req_seed, np.uint32)
+    fw = np.ascontiguousarray(op_flags_wire, np.uint8)
+    obj = np.ascontiguousarray(op_obj, np.uint32)
+    Q, O = int(off.size) - 1, int(obj.size)
+    k, keep = keys.to_c()
+    fl, ep, st = np.zeros(max(O, 1), np.uint8), np.zeros(max(O, 1), np.int64), np.zeros(max(O, 1), np.uint32)
+    pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+    rc = lib.mochi_write1_state_join(Q, O, _ptr(off), _ptr(pad(seed)), _ptr(pad(fw)), _ptr(pad(obj)), ctypes.addressof(k),
+                                     _ptr(fl), _ptr(ep), _ptr(st))
+    if rc != OK:
+        raise MochiError(f"mochi_write1_state_join rc={rc}: {_err(lib)}")
+    return fl[:O], ep[:O], st[:O]
+
+
+def _to_dev(a: np.ndarray, device: int):
+    import torch
+
+    sv = {np.dtype(np.uint8): np.uint8, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64,
+          np.dtype(np.int64): np.int64}
+    a = a if a.size else np.zeros(1, a.dtype)
+    a = a if a.flags.writeable else a.copy()  # torch refuses a read-only view (np.frombuffer)
+    return torch.from_numpy(a.view(sv[a.dtype])).to(torch.device("cuda", device))
+
+
+class DeviceWrite1Requests:
+    """A Write1Requests copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, reqs: "Write1Requests", device: int = 0):
+        a = reqs.arrays()
+        self._set(reqs.n_reqs, int(a["wire"].size), {k: _to_dev(v, device) for k, v in a.items()})
+
+    def _set(self, Q, wire_len, tensors):
+        self.n_reqs, self.wire_len = int(Q), int(wire_len)
+        for k in Write1Requests.DTYPES:
+            setattr(self, k, tensors[k])
+
+    @classmethod
+    def from_tensors(cls, n_reqs: int, **tensors) -> "DeviceWrite1Requests":
+        """Arrays already on the device (uint64 as int64, uint32 as int32), used as they are."""
+        self = cls.__new__(cls)
+        self._set(n_reqs, tensors["wire"].numel(), tensors)
+        return self
+
+    def to_c(self) -> Write1Requests_C:
+        c = Write1Requests_C()
+        c.n_reqs, c.wire_len = self.n_reqs, self.wire_len
+        for k in Write1Requests.DTYPES:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
+
+
+class DeviceWrite1RequestsDecoded:
+    """Device buffers for the outputs of DeviceSigner.request_decode_device, prefilled with
+    `fill`; n_ops is set by the call, the key count lands in the device word n_keys_dev.
+    Tensors carry the ABI widths (uint32 as int32, uint64 as int64)."""
+
+    def __init__(self, n_reqs: int, op_cap: int, device: int = 0, fill: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        sv = {np.uint8: torch.uint8, np.uint32: torch.int32, np.uint64: torch.int64}
+        self.n_reqs, self.op_cap = int(n_reqs), int(op_cap)
+        n = dict(Q=self.n_reqs, Q1=self.n_reqs + 1, O=self.op_cap, K=self.op_cap)
+        pat = lambda dt: int.from_bytes(bytes([fill & 0xFF]) * np.dtype(dt).itemsize, "little", signed=dt != np.uint8)
+        for k, (dt, w) in _W1Q_OUT.items():
+            setattr(self, k, torch.full((max(n[w], 1),), pat(dt), dtype=sv[dt], device=dev))
+        self.n_keys_dev = torch.full((1,), pat(np.uint32), dtype=torch.int32, device=dev)
+        self.n_ops = 0
+
+    def to_c(self) -> Write1RequestsDecoded_C:
+        o = Write1RequestsDecoded_C()
+        for k in _W1Q_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        o.op_cap = self.op_cap
+        return o
+
+    def n_keys(self) -> int:
+        """The key count (a device read: synchronises)."""
+        return int(self.n_keys_dev.cpu().numpy().view(np.uint32)[0])
+
+    def to_host(self, rc: int = OK) -> "Write1RequestsDecoded":
+        """The buffers on the host, whole (as write1_request_decode_into returns them)."""
+        n = dict(Q=self.n_reqs, Q1=self.n_reqs + 1, O=self.op_cap, K=self.op_cap)
+        arr = {k: getattr(self, k).cpu().numpy().view(dt)[:n[w]] for k, (dt, w) in _W1Q_OUT.items()}
+        return Write1RequestsDecoded(rc=rc, n_ops=self.n_ops, n_keys=self.n_keys(), arrays=arr)
+
+
+class DeviceWrite1KeyState:
+    """A Write1KeyState copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, keys: "Write1KeyState", device: int = 0):
+        a = keys.arrays()
+        self.n_keys, self.n_given = int(a["key_flags"].size), int(a["given_ts"].size)
+        for k, v in a.items():
+            setattr(self, k, _to_dev(v, device))
+
+    def to_c(self) -> Write1KeyState_C:
+        c = Write1KeyState_C()
+        c.n_keys, c.n_given = self.n_keys, self.n_given
+        for k in Write1KeyState.DTYPES:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
 
 
 # ---------------------------------------------------------------------------
