@@ -1132,6 +1132,169 @@ int mochi_write1_state_join_device(mochi_signer* s, uint32_t n_reqs, uint32_t n_
                                    uint32_t* op_stored, void* stream);
 
 /* ------------------------------------------------------------------------
+ * RESULT REPLY DECODE: the client's closing round.  The Write2AnsFromServer /
+ * ReadFromServer bodies a client received (MochiProtocol.proto:45-60, 82-87,
+ * 102-105) become the arrays mochi_tally_responses[_device] reads, and the
+ * per-operation values the accepted TransactionResult is coalesced from, with
+ * protobuf-java 3.16.3 parsing semantics (as the Write1 reply decoder:
+ * singular fields last-wins, unknown fields and known field numbers with a
+ * foreign wire type skipped, groups to depth 100, every string strict UTF-8,
+ * every currentCertificate validated as a WriteCertificate all the way down,
+ * in an operation past the transaction's count too; status the low 32 bits of
+ * its varint, existed any non-zero varint).  The bytes are a Byzantine
+ * server's: every read stays inside the response's slice.
+ *
+ *   Write2AnsFromServer = [0A TransactionResult] [12 rid]
+ *   ReadFromServer      = [0A TransactionResult] [12 nonce] [1A rid]
+ *   TransactionResult   = { 0A OperationResult }
+ *   OperationResult     = [0A result] [12 WriteCertificate] [18 existed] [20 status]
+ *
+ * Field 3 is a string in a ReadFromServer alone: invalid UTF-8 in a length-
+ * delimited field 3 makes a read answer MALFORMED and leaves a Write2 answer OK.
+ *
+ * Input.  Response p is wire[resp_off[p], +resp_len[p]) (any alignment; slices
+ * may alias) with payload case resp_kind[p] (MOCHI_RR_*), known from the
+ * envelope.  Request q owns responses [req_resp_off[q], req_resp_off[q+1]) in
+ * arrival order (a CSR over all n_resps) and sent n_ops[q] operations (at most
+ * MOCHI_MAX_OPS_PER_CERT).  Response p of request q owns the n_ops[q] slots
+ * [slot_off[p], +n_ops[q]) of the per-slot arrays: slot_off is the array the
+ * tally takes as status_off, need not be dense or ascending, and the slot runs
+ * of two responses must not overlap here (they are written).  n_resps is at
+ * most 2^24.
+ * ------------------------------------------------------------------------ */
+#define MOCHI_RR_WRITE2_ANS 0 /* WRITE2ANSFROMSERVER */
+#define MOCHI_RR_READ 1       /* READFROMSERVER      */
+#define MOCHI_RR_OTHER 2      /* any other payload: getWrite2AnsFromServer() / getReadFromServer() give the default
+                                 message, 0 operations (MochiDBClient.java:155, :362) */
+typedef struct mochi_result_replies {
+  uint32_t n_resps, n_reqs;      /* P, Q */
+  const uint8_t*  wire;    uint64_t wire_len;
+  const uint64_t* resp_off;      /* [P] */
+  const uint32_t* resp_len;      /* [P] */
+  const uint8_t*  resp_kind;     /* [P] MOCHI_RR_* */
+  const uint32_t* req_resp_off;  /* [Q+1] */
+  const uint32_t* n_ops;         /* [Q] */
+  const uint64_t* slot_off;      /* [P] */
+} mochi_result_replies;
+
+/* Per-response decode status. */
+enum mochi_rr_status {
+  MOCHI_RRS_OK = 0,
+  /* protobuf-java would throw while parsing the body as its message type */
+  MOCHI_RRS_MALFORMED = 1,
+  /* well-formed (validated whole, never malformed) but not decoded: `result`
+   * given more than once (a merge concatenates the lists); an OperationResult
+   * among the request's first n_ops carrying currentCertificate more than once
+   * (the two maps merge: no single slice is the value) */
+  MOCHI_RRS_FALLBACK = 2,
+};
+#define MOCHI_RRO_HAS_CERT 0x01 /* the OperationResult carries a currentCertificate */
+
+/* Output; every array is the caller's.  Offsets point into `wire` (zero copy).
+ * Per response:
+ *   resp_n_ops: the OperationResult count on the wire, whatever it is (more
+ *     than MOCHI_MAX_OPS_PER_CERT too: such a body is validated whole and, as
+ *     its count can equal no n_ops, none of its slots holds a value); 0
+ *     without a `result` and for kind OTHER (not parsed: status OK);
+ *     0xFFFFFFFF for a MALFORMED or FALLBACK response, which so equals no
+ *     n_ops, not even 0: a reply nobody decoded never counts as an empty one.
+ *   resp_rid_* / resp_nonce_*: last occurrence (a Write2 answer has no nonce);
+ *     0 / 0 if not decoded or not parsed.  Here and below, a field that is
+ *     absent gives its message's own offset and length 0.
+ * Per slot j < n_ops[q] of response p, at slot_off[p] + j: op_status =
+ * OperationResult.status (0 OK, 1 WRONG_SHARD), 0xFF for a value outside
+ * 0..254 -- the array is mochi_tally_responses' `status` --; op_existed;
+ * op_flags = MOCHI_RRO_*; the `result` string and the currentCertificate as
+ * slices, the certificate validated and otherwise opaque.  All n_ops[q] slots
+ * of every response are written and nothing else is: the slots at or past the
+ * response's count, and all slots of a response that is not OK, read absent
+ * (status 0xFF, existed 0, flags 0, slices 0 / 0). */
+typedef struct mochi_result_decoded {
+  uint8_t*  resp_status;     /* [P] enum mochi_rr_status */
+  uint32_t* resp_n_ops;      /* [P] */
+  uint64_t* resp_rid_off;    /* [P] */
+  uint32_t* resp_rid_len;    /* [P] */
+  uint64_t* resp_nonce_off;  /* [P] */
+  uint32_t* resp_nonce_len;  /* [P] */
+  uint8_t*  op_status;       /* per slot */
+  uint8_t*  op_existed;
+  uint8_t*  op_flags;
+  uint64_t* op_result_off;
+  uint32_t* op_result_len;
+  uint64_t* op_cert_off;
+  uint32_t* op_cert_len;
+} mochi_result_decoded;
+
+/* Host form: every array in host memory, no context, no GPU.  MOCHI_EINVAL for
+ * a response slice outside `wire`, a req_resp_off that is not a CSR over
+ * n_resps, an n_ops above MOCHI_MAX_OPS_PER_CERT, a resp_kind that is no
+ * MOCHI_RR_*, more than 2^24 responses, responses without a request, or a
+ * NULL array (with n_resps > 0 every array of both structs is read or
+ * written).  With n_resps == 0 no pointer is needed and nothing is written. */
+int mochi_result_reply_decode(const mochi_result_replies* replies, mochi_result_decoded* out);
+
+/* Device form: every array of `replies` and `out` in DEVICE memory, the structs
+ * themselves on the host; scratch is the context's.  No host wait: every output
+ * size follows from the caller's own arrays, so the call returns with all its
+ * kernels enqueued on `stream` (hipStream_t; NULL = null stream), and
+ * mochi_tally_responses_device (resp_off = req_resp_off, status_off =
+ * slot_off, status = op_status) and mochi_result_coalesce_device may be
+ * enqueued behind it at once.  The caller's own arrays are trusted, the bytes
+ * of `wire` are not. */
+int mochi_result_reply_decode_device(mochi_ctx* ctx, const mochi_result_replies* replies, mochi_result_decoded* out,
+                                     void* stream);
+/* Per-kernel device time (ms) of the last mochi_result_reply_decode_device call
+ * made while profiling was on (mochi_ctx_set_profiling): [0] k_rr_resp, [1] the
+ * operation scan, [2] k_rr_ops, [3] k_rr_final.  Waits for that call.
+ * n_kernels <= 4. */
+int mochi_ctx_read_result_decode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n_kernels);
+
+/* COALESCE: the TransactionResult the client returns once the tally accepted
+ * (MochiDBClient.java:177-179 / :384-386): per op, the result of the LAST
+ * response that did not answer WRONG_SHARD.  Inputs: the decoder's request CSR,
+ * n_ops, slot_off and per-slot arrays, and the tally's chosen / chosen_off /
+ * accept_bits. */
+typedef struct mochi_result_tallied {
+  uint32_t n_reqs, _pad0;        /* Q */
+  const uint32_t* req_resp_off;  /* [Q+1] */
+  const uint32_t* n_ops;         /* [Q] */
+  const int32_t*  chosen;        /* the tally's: index among the request's responses, or -1 */
+  const uint64_t* chosen_off;    /* [Q] */
+  const uint32_t* accept_bits;   /* [ceil(Q/32)] */
+  const uint64_t* slot_off;      /* [P] */
+  const uint8_t*  op_status;     /* per slot, as mochi_result_decoded */
+  const uint8_t*  op_existed;
+  const uint8_t*  op_flags;
+  const uint64_t* op_result_off;
+  const uint32_t* op_result_len;
+  const uint64_t* op_cert_off;
+  const uint32_t* op_cert_len;
+  const uint64_t* out_off;       /* [Q] where request q's n_ops[q] entries start in the outputs */
+} mochi_result_tallied;
+/* Per (request, op) at out_off[q] + j: resp = the chosen response's index among
+ * ALL responses (req_resp_off[q] + chosen), and that response's slot values.  A
+ * request whose accept bit is 0 gets resp 0xFFFFFFFF and absent values (status
+ * 0xFF, existed 0, flags 0, slices 0 / 0) in all its ops. */
+typedef struct mochi_result_coalesced {
+  uint32_t* resp;
+  uint8_t*  status;
+  uint8_t*  existed;
+  uint8_t*  flags;
+  uint64_t* result_off;
+  uint32_t* result_len;
+  uint64_t* cert_off;
+  uint32_t* cert_len;
+} mochi_result_coalesced;
+/* Host form.  MOCHI_EINVAL for a NULL array, a req_resp_off that descends, an
+ * n_ops above MOCHI_MAX_OPS_PER_CERT, or a chosen index of an accepted request
+ * at or past its response count.  With n_reqs == 0 no pointer is needed. */
+int mochi_result_coalesce(const mochi_result_tallied* tallied, mochi_result_coalesced* out);
+/* Device form: every array in DEVICE memory; one kernel on `stream` on the
+ * current device (lane = request), no host wait, no scratch; the inputs are
+ * trusted. */
+int mochi_result_coalesce_device(const mochi_result_tallied* tallied, mochi_result_coalesced* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps
  * (Write2ToServerRequestHandler.handle -> processWrite2ToServer on a 2..20
  * thread pool, MochiServer.java:36-40), coalesced across threads into one

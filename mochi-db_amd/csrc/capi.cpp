@@ -15,6 +15,7 @@
 
 #include "ctx.h"
 #include "mont.h"
+#include "result_decode.h"
 #include "w1_decode.h"
 #include "w1_issue.h"
 #include "w1_reply.h"
@@ -1756,6 +1757,103 @@ int mochi_write1_state_join_device(mochi_signer* s, uint32_t n_reqs, uint32_t n_
   if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", s->device);
   const mochi::w1q::JoinArgs a{n_reqs, n_ops, req_op_off, req_seed, op_flags_wire, op_obj, *keys, op_flags, op_epoch, op_stored};
   HIP_TRY(mochi::launch_w1q_join(a, (hipStream_t)stream));
+  return MOCHI_OK;
+}
+
+}  // extern "C"
+
+// ---- result reply decoder and coalescing (result_decode.hip / result_decode_host.cpp) ----
+namespace {
+
+int check_result_replies(const mochi_result_replies* r, const mochi_result_decoded* o) {
+  if (!r || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (r->n_resps > mochi::w1d::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
+  if (!r->n_resps) return MOCHI_OK;
+  if (!r->n_reqs) return fail(MOCHI_EINVAL, "responses without a request");
+  if (!r->resp_off || !r->resp_len || !r->resp_kind || (!r->wire && r->wire_len))
+    return fail(MOCHI_EINVAL, "wire / resp_off / resp_len / resp_kind required");
+  if (!r->req_resp_off || !r->n_ops || !r->slot_off) return fail(MOCHI_EINVAL, "req_resp_off / n_ops / slot_off required");
+  if (!o->resp_status || !o->resp_n_ops || !o->resp_rid_off || !o->resp_rid_len || !o->resp_nonce_off ||
+      !o->resp_nonce_len)
+    return fail(MOCHI_EINVAL, "the per-response outputs are required");
+  if (!o->op_status || !o->op_existed || !o->op_flags || !o->op_result_off || !o->op_result_len || !o->op_cert_off ||
+      !o->op_cert_len)
+    return fail(MOCHI_EINVAL, "the per-slot outputs are required");
+  return MOCHI_OK;
+}
+
+int check_result_tallied(const mochi_result_tallied* t, const mochi_result_coalesced* o) {
+  if (!t || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (!t->n_reqs) return MOCHI_OK;
+  if (!t->req_resp_off || !t->n_ops || !t->chosen || !t->chosen_off || !t->accept_bits || !t->slot_off || !t->out_off)
+    return fail(MOCHI_EINVAL, "req_resp_off / n_ops / chosen / chosen_off / accept_bits / slot_off / out_off required");
+  if (!t->op_status || !t->op_existed || !t->op_flags || !t->op_result_off || !t->op_result_len || !t->op_cert_off ||
+      !t->op_cert_len)
+    return fail(MOCHI_EINVAL, "the per-slot inputs are required");
+  if (!o->resp || !o->status || !o->existed || !o->flags || !o->result_off || !o->result_len || !o->cert_off ||
+      !o->cert_len)
+    return fail(MOCHI_EINVAL, "the coalesced outputs are required");
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mochi_result_reply_decode(const mochi_result_replies* r, mochi_result_decoded* o) {
+  int rc = check_result_replies(r, o);
+  if (rc || !r->n_resps) return rc;
+  const char* err = nullptr;
+  rc = mochi_host::result_reply_decode(r, o, &err);
+  return rc ? fail(rc, "mochi_result_reply_decode: %s", err) : MOCHI_OK;
+}
+
+int mochi_result_reply_decode_device(mochi_ctx* c, const mochi_result_replies* r, mochi_result_decoded* o,
+                                     void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  int rc = check_result_replies(r, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  EncState& x = c->rr;
+  x.ev_valid = false;
+  if (!r->n_resps) return MOCHI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  mochi::RRArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.in = *r;
+  a.v.out = *o;
+  a.P = r->n_resps;
+  if ((rc = x.begin(a, mochi::rr_layout, a.P + 1, 0, c->profiling, mochi::kRREvents))) return rc;
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_rr_decode(a, st));
+  x.ev_valid = a.ev != nullptr;
+  HIP_TRY(c->order.release(st));
+  return MOCHI_OK;
+}
+
+int mochi_ctx_read_result_decode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n_kernels) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  static const int kSpan[mochi::kRRStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+  return c->rr.read_profile(kSpan, mochi::kRRStages, kernel_ms, n_kernels,
+                            "no result reply decode call was made while profiling was on");
+}
+
+int mochi_result_coalesce(const mochi_result_tallied* t, mochi_result_coalesced* o) {
+  int rc = check_result_tallied(t, o);
+  if (rc || !t->n_reqs) return rc;
+  const char* err = nullptr;
+  rc = mochi_host::result_coalesce(t, o, &err);
+  return rc ? fail(rc, "mochi_result_coalesce: %s", err) : MOCHI_OK;
+}
+
+int mochi_result_coalesce_device(const mochi_result_tallied* t, mochi_result_coalesced* o, void* stream) {
+  int rc = check_result_tallied(t, o);
+  if (rc || !t->n_reqs) return rc;
+  HIP_TRY(mochi::launch_rr_coalesce(*t, *o, (hipStream_t)stream));
   return MOCHI_OK;
 }
 

@@ -202,6 +202,7 @@ struct mochi_ctx {
   mochi::EncState w2e;  // Write2 encoder (w2_encode.hip); its total is the wire size
   mochi::EncState w1d;  // Write1 reply decoder (w1_decode.hip); its totals are the grant and certificate counts
   mochi::DevBuf w1d_sig;  // ... and its signature sources, sized once the grant total is known
+  mochi::EncState rr;   // result reply decoder (result_decode.hip); it waits for no total
   // the last host-path call's certificate accept bitmap on the device (a slice
   // of dev_out, valid until the next call on this context; nullptr when the
   // device copy is not the final verdict, e.g. after host fallback decisions):

@@ -217,6 +217,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_signer_read_request_profile.argtypes = [vp, vp, u32]
     lib.mochi_write1_state_join.argtypes = [u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mochi_write1_state_join_device.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mochi_result_reply_decode.argtypes = [vp, vp]
+    lib.mochi_result_reply_decode_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_ctx_read_result_decode_profile.argtypes = [vp, vp, u32]
+    lib.mochi_result_coalesce.argtypes = [vp, vp]
+    lib.mochi_result_coalesce_device.argtypes = [vp, vp, vp]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -588,6 +593,22 @@ class Verifier:
         if self.lib.mochi_ctx_read_w1_decode_profile(self.ctx, _ptr(ms), ms.size) != OK:
             raise MochiError(f"mochi_ctx_read_w1_decode_profile: {_err(self.lib)}")
         return dict(zip(W1_DECODE_STAGES, (float(x) for x in ms)))
+
+    def result_reply_decode_device(self, dreplies: "DeviceResultReplies", out: "DeviceResultDecoded",
+                                   stream: int = 0) -> None:
+        """mochi_result_reply_decode_device: device-resident Write2 / read answer bodies -> the
+        arrays of `out`.  Returns with everything enqueued on `stream`; it waits for nothing."""
+        r, o = dreplies.to_c(), out.to_c()
+        rc = self.lib.mochi_result_reply_decode_device(self.ctx, ctypes.addressof(r), ctypes.addressof(o), stream or None)
+        if rc != OK:
+            raise MochiError(f"mochi_result_reply_decode_device rc={rc}: {_err(self.lib)}")
+
+    def read_result_decode_profile(self) -> dict:
+        """Per-kernel ms of the last result_reply_decode_device call made with set_profiling(True)."""
+        ms = np.zeros(len(RESULT_DECODE_STAGES), np.float32)
+        if self.lib.mochi_ctx_read_result_decode_profile(self.ctx, _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_result_decode_profile: {_err(self.lib)}")
+        return dict(zip(RESULT_DECODE_STAGES, (float(x) for x in ms)))
 
     def decode_write2(self, wb) -> dict:
         """The device decoder's SoA view of the messages (inspection / tests)."""
@@ -2359,6 +2380,218 @@ class DeviceWrite1KeyState:
         for k in Write1KeyState.DTYPES:
             setattr(c, k, getattr(self, k).data_ptr())
         return c
+
+
+# ---------------------------------------------------------------------------
+# Result reply decode (the client's closing round): Write2AnsFromServer / ReadFromServer
+# bodies -> the arrays tally_responses reads and the per-op values it coalesces
+# ---------------------------------------------------------------------------
+RR_WRITE2_ANS, RR_READ, RR_OTHER = range(3)
+RRS_OK, RRS_MALFORMED, RRS_FALLBACK = range(3)
+RRO_HAS_CERT = 0x01
+RR_UNDECODED = 0xFFFFFFFF  # resp_n_ops of a MALFORMED / FALLBACK response
+RESULT_DECODE_STAGES = ("k_rr_resp", "op_scan", "k_rr_ops", "k_rr_final")
+
+
+class ResultReplies_C(ctypes.Structure):
+    _fields_ = [("n_resps", ctypes.c_uint32), ("n_reqs", ctypes.c_uint32), ("wire", ctypes.c_void_p),
+                ("wire_len", ctypes.c_uint64), ("resp_off", ctypes.c_void_p), ("resp_len", ctypes.c_void_p),
+                ("resp_kind", ctypes.c_void_p), ("req_resp_off", ctypes.c_void_p), ("n_ops", ctypes.c_void_p),
+                ("slot_off", ctypes.c_void_p)]
+
+
+# output arrays by what they are indexed with: "P" responses, "S" slots
+_RR_OUT = dict(resp_status=(np.uint8, "P"), resp_n_ops=(np.uint32, "P"), resp_rid_off=(np.uint64, "P"),
+               resp_rid_len=(np.uint32, "P"), resp_nonce_off=(np.uint64, "P"), resp_nonce_len=(np.uint32, "P"),
+               op_status=(np.uint8, "S"), op_existed=(np.uint8, "S"), op_flags=(np.uint8, "S"),
+               op_result_off=(np.uint64, "S"), op_result_len=(np.uint32, "S"), op_cert_off=(np.uint64, "S"),
+               op_cert_len=(np.uint32, "S"))
+_RR_SLOT = tuple(k for k, (dt, w) in _RR_OUT.items() if w == "S")
+# the coalesced outputs, one entry per (request, op)
+_RC_OUT = dict(resp=np.uint32, status=np.uint8, existed=np.uint8, flags=np.uint8, result_off=np.uint64,
+               result_len=np.uint32, cert_off=np.uint64, cert_len=np.uint32)
+
+
+class ResultDecoded_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _RR_OUT]
+
+
+class ResultTallied_C(ctypes.Structure):
+    _fields_ = [("n_reqs", ctypes.c_uint32), ("_pad0", ctypes.c_uint32)] + \
+        [(k, ctypes.c_void_p) for k in ("req_resp_off", "n_ops", "chosen", "chosen_off", "accept_bits", "slot_off") +
+         _RR_SLOT + ("out_off",)]
+
+
+class ResultCoalesced_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _RC_OUT]
+
+
+@dataclass
+class ResultReplies:
+    """The answers a client received in its closing round (mochi_result_replies, host arrays)."""
+
+    wire: np.ndarray  # uint8
+    resp_off: np.ndarray  # uint64 [P]
+    resp_len: np.ndarray  # uint32 [P]
+    resp_kind: np.ndarray  # uint8 [P] RR_*
+    req_resp_off: np.ndarray  # uint32 [Q+1]
+    n_ops: np.ndarray  # uint32 [Q]
+    slot_off: np.ndarray  # uint64 [P]
+
+    DTYPES = dict(wire=np.uint8, resp_off=np.uint64, resp_len=np.uint32, resp_kind=np.uint8, req_resp_off=np.uint32,
+                  n_ops=np.uint32, slot_off=np.uint64)
+
+    @property
+    def n_resps(self) -> int:
+        return int(np.asarray(self.resp_off).shape[0])
+
+    @property
+    def n_reqs(self) -> int:
+        return int(np.asarray(self.n_ops).shape[0])
+
+    @property
+    def n_slots(self) -> int:
+        """Entries the per-slot arrays need: the end of the furthest slot run."""
+        if not self.n_resps:
+            return 0
+        per = np.repeat(np.asarray(self.n_ops, np.uint64), np.diff(np.asarray(self.req_resp_off, np.int64)))
+        return int((np.asarray(self.slot_off, np.uint64) + per).max())
+
+    def arrays(self) -> dict:
+        return {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in self.DTYPES.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = ResultReplies_C()
+        c.n_resps, c.n_reqs, c.wire_len = self.n_resps, self.n_reqs, int(arrs["wire"].size)
+        for k, a in arrs.items():
+            if a.size == 0:  # an empty array still gets a valid address
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def result_reply_decode(replies: "ResultReplies", n_slots: Optional[int] = None, fill: int = 0) -> dict:
+    """mochi_result_reply_decode (host form) into buffers prefilled with `fill`: the arrays
+    of mochi_result_decoded by name, the per-slot ones n_slots long (default: replies.n_slots)."""
+    lib = load_library()
+    r, keep = replies.to_c()
+    n = dict(P=replies.n_resps, S=replies.n_slots if n_slots is None else int(n_slots))
+    arr = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _RR_OUT.items()}
+    o = ResultDecoded_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a if a.size else np.zeros(1, a.dtype)))
+    rc = lib.mochi_result_reply_decode(ctypes.addressof(r), ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_result_reply_decode rc={rc}: {_err(lib)}")
+    return arr
+
+
+def _tallied_c(replies_c, slots: dict, chosen, chosen_off, accept_bits, out_off) -> ResultTallied_C:
+    """Pointers (ints) in, the C struct out."""
+    t = ResultTallied_C()
+    t.n_reqs = replies_c.n_reqs
+    t.req_resp_off, t.n_ops, t.slot_off = replies_c.req_resp_off, replies_c.n_ops, replies_c.slot_off
+    t.chosen, t.chosen_off, t.accept_bits, t.out_off = chosen, chosen_off, accept_bits, out_off
+    for k in _RR_SLOT:
+        setattr(t, k, slots[k])
+    return t
+
+
+def result_coalesce(replies: "ResultReplies", decoded: dict, chosen: np.ndarray, chosen_off: np.ndarray,
+                    accept_bits: np.ndarray, out_off: np.ndarray, n_out: int, fill: int = 0) -> dict:
+    """mochi_result_coalesce (host form): the tally's chosen / chosen_off / accept_bits and the
+    decoder's per-slot arrays -> the arrays of mochi_result_coalesced, n_out long, prefilled."""
+    lib = load_library()
+    r, keep = replies.to_c()
+    some = lambda a, dt: np.ascontiguousarray(a if np.asarray(a).size else np.zeros(1, dt), dt)
+    ins = [some(chosen, np.int32), some(chosen_off, np.uint64), some(accept_bits, np.uint32), some(out_off, np.uint64)]
+    slots = {k: some(decoded[k], _RR_OUT[k][0]) for k in _RR_SLOT}
+    t = _tallied_c(r, {k: _ptr(a) for k, a in slots.items()}, *[_ptr(a) for a in ins])
+    arr = {k: np.full(int(n_out) * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, dt in _RC_OUT.items()}
+    o = ResultCoalesced_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a if a.size else np.zeros(1, a.dtype)))
+    rc = lib.mochi_result_coalesce(ctypes.addressof(t), ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_result_coalesce rc={rc}: {_err(lib)}")
+    return arr
+
+
+class DeviceResultReplies:
+    """A ResultReplies copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, replies: "ResultReplies", device: int = 0):
+        self.n_resps, self.n_reqs = replies.n_resps, replies.n_reqs
+        self.wire_len = int(np.asarray(replies.wire).size)
+        for k, a in replies.arrays().items():
+            setattr(self, k, _to_dev(a, device))
+
+    def to_c(self) -> ResultReplies_C:
+        c = ResultReplies_C()
+        c.n_resps, c.n_reqs, c.wire_len = self.n_resps, self.n_reqs, self.wire_len
+        for k in ResultReplies.DTYPES:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
+
+
+def _dev_full(n: int, dt, fill: int, device: int):
+    import torch
+
+    sv = {np.uint8: torch.uint8, np.uint32: torch.int32, np.int32: torch.int32, np.uint64: torch.int64}
+    pat = int.from_bytes(bytes([fill & 0xFF]) * np.dtype(dt).itemsize, "little", signed=dt != np.uint8)
+    return torch.full((max(int(n), 1),), pat, dtype=sv[dt], device=torch.device("cuda", device))
+
+
+class DeviceResultDecoded:
+    """Device buffers for the outputs of Verifier.result_reply_decode_device, prefilled with
+    `fill`.  Tensors carry the ABI widths (uint32 as int32, uint64 as int64)."""
+
+    def __init__(self, n_resps: int, n_slots: int, device: int = 0, fill: int = 0):
+        self.n = dict(P=int(n_resps), S=int(n_slots))
+        for k, (dt, w) in _RR_OUT.items():
+            setattr(self, k, _dev_full(self.n[w], dt, fill, device))
+
+    def to_c(self) -> ResultDecoded_C:
+        o = ResultDecoded_C()
+        for k in _RR_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        return o
+
+    def to_host(self) -> dict:
+        """The buffers on the host, whole (as result_reply_decode returns them)."""
+        return {k: getattr(self, k).cpu().numpy().view(dt)[:self.n[w]] for k, (dt, w) in _RR_OUT.items()}
+
+
+class DeviceResultCoalesced:
+    """Device buffers for the outputs of result_coalesce_device, prefilled with `fill`."""
+
+    def __init__(self, n_out: int, device: int = 0, fill: int = 0):
+        self.n_out = int(n_out)
+        for k, dt in _RC_OUT.items():
+            setattr(self, k, _dev_full(self.n_out, dt, fill, device))
+
+    def to_c(self) -> ResultCoalesced_C:
+        o = ResultCoalesced_C()
+        for k in _RC_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        return o
+
+    def to_host(self) -> dict:
+        return {k: getattr(self, k).cpu().numpy().view(dt)[:self.n_out] for k, dt in _RC_OUT.items()}
+
+
+def result_coalesce_device(dreplies: "DeviceResultReplies", decoded: "DeviceResultDecoded", chosen, chosen_off,
+                           accept_bits, out_off, out: "DeviceResultCoalesced", stream: int = 0) -> None:
+    """mochi_result_coalesce_device: one kernel on `stream`, no wait.  chosen / chosen_off /
+    accept_bits are the tally's device tensors, out_off an int64 tensor [Q]."""
+    lib = load_library()
+    t = _tallied_c(dreplies.to_c(), {k: getattr(decoded, k).data_ptr() for k in _RR_SLOT}, chosen.data_ptr(),
+                   chosen_off.data_ptr(), accept_bits.data_ptr(), out_off.data_ptr())
+    o = out.to_c()
+    rc = lib.mochi_result_coalesce_device(ctypes.addressof(t), ctypes.addressof(o), stream or None)
+    if rc != OK:
+        raise MochiError(f"mochi_result_coalesce_device rc={rc}: {_err(lib)}")
 
 
 # ---------------------------------------------------------------------------
