@@ -550,6 +550,8 @@ enum mochi_enc_status {
   MOCHI_ENC_BAD_GRANT = 1,  /* a grant does not parse (or lies outside grant_bytes) */
   MOCHI_ENC_BAD_SIGNER = 2, /* an mg_signer outside the id table                    */
   MOCHI_ENC_TOO_LONG = 3,   /* the message would be 2^31 bytes or more              */
+  MOCHI_ENC_BAD_OP = 4,     /* answer encoder alone: an op slot of the response reads absent
+                               (op_status 0xFF); the response's size is then not computed    */
 };
 
 /* A safe upper bound on the wire size, from the counts and the two blob
@@ -1293,6 +1295,167 @@ int mochi_result_coalesce(const mochi_result_tallied* tallied, mochi_result_coal
  * current device (lane = request), no host wait, no scratch; the inputs are
  * trusted. */
 int mochi_result_coalesce_device(const mochi_result_tallied* tallied, mochi_result_coalesced* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Answer ENCODER (the server's closing round): the inverse of
+ * mochi_result_reply_decode.  The Write2AnsFromServer / ReadFromServer bodies
+ * of a batch from caller arrays, byte for byte what protobuf-java writes
+ * (InMemoryDataStore.java:641-666, :521-574, :582-587, :75-103, :201-231):
+ *
+ *   Write2AnsFromServer = 0A len TransactionResult   always, also when empty (0A 00: setResult is always called)
+ *                         [12 rid]                   iff non-empty
+ *   ReadFromServer      = 0A len TransactionResult  [12 nonce] [1A rid]   each string iff non-empty
+ *   TransactionResult   = { 0A len OperationResult } one per op, also when empty (0A 00)
+ *   OperationResult     = [0A result] iff non-empty
+ *                         [12 len cert] iff HAS_CERT, also when empty (12 00: processRead sets the default instance)
+ *                         [18 01] iff existed
+ *                         [20 varint(status)] iff status != 0
+ *
+ * Input.  Response p has kind resp_kind[p] (MOCHI_RR_WRITE2_ANS / MOCHI_RR_READ;
+ * MOCHI_RR_OTHER: no body, length 0, status OK), resp_n_ops[p] operations (at
+ * most MOCHI_MAX_OPS_PER_CERT) in the slots [slot_off[p], +resp_n_ops[p]) of
+ * the per-slot arrays, which are n_slots long; slot_off need not be dense or
+ * ascending and the slot runs of two responses must not overlap (as in the
+ * decoder).  rid and nonce are slices of `ids`; either pair of arrays may be
+ * NULL (empty); a Write2 answer has no nonce.  Per slot: op_status 0..254 is
+ * written as a varint (128..254 take two bytes), 0xFF -- the decoder's
+ * "absent" mark -- makes the response MOCHI_ENC_BAD_OP; op_existed;
+ * op_flags = MOCHI_RAO_*; the `result` string and the certificate as slices of
+ * `wire` (the received request bytes: an applied op answers with the incoming
+ * certificate and its own operand2) or, by flag, of `store` (stored values and
+ * certificates).  Slices may alias and have any alignment; certificates are
+ * opaque bytes, copied as given.
+ * ------------------------------------------------------------------------ */
+#define MOCHI_RAO_HAS_CERT 0x01     /* = MOCHI_RRO_HAS_CERT: currentCertificate is written, also when empty */
+#define MOCHI_RAO_RESULT_STORE 0x02 /* op_result_off points into `store`, not `wire` */
+#define MOCHI_RAO_CERT_STORE 0x04   /* op_cert_off points into `store`, not `wire`   */
+typedef struct mochi_result_answers {
+  uint32_t n_resps, n_slots;     /* P, S */
+  const uint8_t*  wire;    uint64_t wire_len;
+  const uint8_t*  store;   uint64_t store_len;
+  const uint8_t*  ids;     uint64_t ids_len;
+  const uint8_t*  resp_kind;     /* [P] MOCHI_RR_* */
+  const uint32_t* resp_n_ops;    /* [P] */
+  const uint64_t* slot_off;      /* [P] */
+  const uint64_t* rid_off;       /* [P] into ids; NULL with rid_len = every rid empty */
+  const uint32_t* rid_len;
+  const uint64_t* nonce_off;     /* [P] into ids; NULL with nonce_len = every nonce empty */
+  const uint32_t* nonce_len;
+  const uint8_t*  op_status;     /* [S] */
+  const uint8_t*  op_existed;
+  const uint8_t*  op_flags;      /* MOCHI_RAO_* */
+  const uint64_t* op_result_off;
+  const uint32_t* op_result_len;
+  const uint64_t* op_cert_off;
+  const uint32_t* op_cert_len;
+} mochi_result_answers;
+
+/* A safe wire_cap from counts and blob lengths alone (n_ops: the sum of resp_n_ops). */
+uint64_t mochi_result_reply_encode_bound(uint32_t n_resps, uint64_t n_ops, uint64_t wire_len, uint64_t store_len,
+                                         uint64_t ids_len);
+
+/* Host form: every array in host memory.  Outputs as mochi_write1_reply_encode:
+ * message p is wire_out[msg_off[p], +msg_len[p]), packed back to back in
+ * response order with 64-bit offsets; status[p] is enum mochi_enc_status
+ * (MOCHI_ENC_TOO_LONG: 2^31 bytes or more; it and MOCHI_ENC_BAD_OP give length
+ * 0); *wire_len the total.  MOCHI_EINVAL, with *wire_len set and no byte
+ * written, when wire_cap is smaller; MOCHI_EINVAL also for a slice outside its
+ * blob, a slot run outside n_slots, a resp_n_ops above MOCHI_MAX_OPS_PER_CERT,
+ * a kind that is no MOCHI_RR_*, or a NULL required array.  With n_resps == 0 no
+ * pointer but wire_len is needed and nothing is written. */
+int mochi_result_reply_encode(const mochi_result_answers* answers, uint8_t* wire_out, uint64_t wire_cap,
+                              uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len);
+
+/* Device form: every array of `answers` and every output in DEVICE memory, the
+ * struct itself on the host; scratch is the context's.  The caller's arrays are
+ * trusted.  The two capacity modes of mochi_write1_reply_encode_device:
+ * wire_len (host) non-NULL: one wait for the total, MOCHI_EINVAL with the needed
+ * size and no byte written if it exceeds wire_cap; wire_len NULL and
+ * wire_len_dev (device) non-NULL: no host wait, the total goes to *wire_len_dev,
+ * and every kernel that writes wire_out reads it first and writes nothing if it
+ * exceeds wire_cap (msg_off / msg_len / status are written either way). */
+int mochi_result_reply_encode_device(mochi_ctx* ctx, const mochi_result_answers* answers, uint8_t* wire_out,
+                                     uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len, uint8_t* status,
+                                     uint64_t* wire_len, uint64_t* wire_len_dev, void* stream);
+/* Per-kernel device time (ms) of the last mochi_result_reply_encode_device call
+ * made while profiling was on: [0] k_rae_size, [1] the offset scan, [2]
+ * k_rae_hdr, [3] k_rae_copy.  Waits for that call.  n_kernels <= 4. */
+int mochi_ctx_read_result_encode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n_kernels);
+
+/* ------------------------------------------------------------------------
+ * Write2 answer PLAN: from the verifier's outputs to the encoder's input.  Per
+ * message of the mochi_write2_batch the verify call took (op_flags_off is
+ * required here), from msg_status / cert_accept_bits / op_decision as
+ * mochi_verify_write2[_device] left them and the store's side of every op:
+ *   MOCHI_W2A_REPLY     msg_status OK, accepted, every decision APPLY, READ or
+ *     WRONG_SHARD: resp_kind = MOCHI_RR_WRITE2_ANS, resp_n_ops = the op count.
+ *     WRONG_SHARD -> status 1 alone.  APPLY -> status 0, result = the op's
+ *     operand2 (a slice of batch->wire), existed = (action == WRITE), HAS_CERT,
+ *     certificate = the message's field 1 (a slice of batch->wire; absent:
+ *     length 0).  READ -> status 0, existed 1, result = the stored value
+ *     (RESULT_STORE), certificate = the stored one (CERT_STORE; HAS_CERT iff
+ *     MOCHI_W2A_HAS_STORED_CERT).
+ *   MOCHI_W2A_NO_REPLY  the reference threw (not accepted, a FAILED / SKIPPED
+ *     decision, msg_status MALFORMED / OPS_MISMATCH, a READ of an op marked
+ *     MOCHI_W2A_VALUE_NULL, or a body whose operations the walk cannot match to
+ *     op_flags_off): resp_kind = MOCHI_RR_OTHER, every slot absent.
+ *   MOCHI_W2A_HOST      msg_status FALLBACK but accepted (merged or repeated
+ *     fields have no single slice): resp_kind = MOCHI_RR_OTHER, every slot
+ *     absent; the caller builds this answer.
+ * The walk takes the last length-delimited field 1 of the body and, per
+ * Operation of field 2, the last `action` varint (low 32 bits) and the last
+ * length-delimited field 3; every read stays inside the message's slice.  An
+ * absent operand2 gives the Operation's own offset and length 0, an absent
+ * certificate the message's own offset and length 0; WRONG_SHARD slots and a
+ * READ without a stored certificate carry offset 0 / length 0.
+ * Message m owns the slots [slot_off[m], +its op count) of the per-slot outputs,
+ * which are n_slots long; all of them are written and nothing else is.
+ * Dependencies between messages of one batch are the caller's, as for verify.
+ * ------------------------------------------------------------------------ */
+#define MOCHI_W2A_REPLY 0
+#define MOCHI_W2A_NO_REPLY 1
+#define MOCHI_W2A_HOST 2
+#define MOCHI_W2A_HAS_STORED_CERT 0x01 /* the key's container holds a certificate                      */
+#define MOCHI_W2A_VALUE_NULL 0x02      /* getValue() is null: setResult(null) throws (:567), no reply */
+typedef struct mochi_write2_answer_source {
+  const uint8_t*  msg_status;          /* [M] enum mochi_msg_status */
+  const uint32_t* cert_accept_bits;    /* [ceil(M/32)] */
+  const uint8_t*  op_decision;         /* [O] enum mochi_op_decision, O = op_flags_off[M] */
+  const uint64_t* op_value_off;        /* [O] into the store blob */
+  const uint32_t* op_value_len;
+  const uint64_t* op_stored_cert_off;  /* [O] into the store blob */
+  const uint32_t* op_stored_cert_len;
+  const uint8_t*  op_store_flags;      /* [O] MOCHI_W2A_* bits */
+  uint64_t store_len;                  /* size of the store blob (the host form checks slices against it) */
+  const uint64_t* slot_off;            /* [M] */
+  uint32_t n_slots, _pad0;
+} mochi_write2_answer_source;
+/* The arrays of a mochi_result_answers with n_resps = M (wire = batch->wire,
+ * store = the store blob), and the plan's verdict per message. */
+typedef struct mochi_write2_answer_planned {
+  uint8_t*  plan_status;     /* [M] MOCHI_W2A_* */
+  uint8_t*  resp_kind;       /* [M] */
+  uint32_t* resp_n_ops;      /* [M] */
+  uint8_t*  op_status;       /* [S] */
+  uint8_t*  op_existed;
+  uint8_t*  op_flags;
+  uint64_t* op_result_off;
+  uint32_t* op_result_len;
+  uint64_t* op_cert_off;
+  uint32_t* op_cert_len;
+} mochi_write2_answer_planned;
+/* Host form.  MOCHI_EINVAL for a NULL array, a message slice outside wire, an
+ * op_flags_off that is not a CSR, a slot run outside n_slots, or a stored slice
+ * outside store_len.  With n_msgs == 0 no pointer is needed. */
+int mochi_write2_answer_plan(const mochi_write2_batch* batch, const mochi_write2_answer_source* src,
+                             mochi_write2_answer_planned* out);
+/* Device form: every array in DEVICE memory; one kernel (k_w2a_plan, lane =
+ * message) on `stream` on the current device, no host wait, no scratch: it may
+ * be enqueued right behind mochi_verify_write2_device, and
+ * mochi_result_reply_encode_device right behind it.  The caller's own arrays
+ * are trusted, the bytes of `wire` are not. */
+int mochi_write2_answer_plan_device(const mochi_write2_batch* batch, const mochi_write2_answer_source* src,
+                                    mochi_write2_answer_planned* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps

@@ -1,0 +1,209 @@
+// result_encode_check — host-only memory check of the Write2 answer plan's walk and of
+// the answer encoder (csrc/result_encode.h through its host forms,
+// csrc/result_encode_host.cpp: the code the kernels of result_encode.hip run too).
+// Every truncation and every single-bit flip of three Write2ToServer bodies (one
+// operation, 64 operations, unknown fields and groups at every level) is planned from the
+// END of a heap buffer of exactly its size with msg_status forced OK and the accept bit
+// set -- what the walk may rely on is its own bounds alone --, into slot arrays of
+// exactly the operation count, and the plan is encoded into a buffer of exactly the size
+// the encoder asks for: `make result_encode_check` builds it with the address and
+// undefined-behaviour sanitizers and runs it, so a read past a body, a slice past a blob
+// or a write past the wire stops it.  It needs no GPU.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../mochi-db_amd/csrc/result_encode.h"
+
+static int g_failed = 0;
+#define CHECK(cond, ...)                   \
+  do {                                     \
+    if (!(cond)) {                         \
+      g_failed++;                          \
+      fprintf(stderr, "FAIL %s: ", #cond); \
+      fprintf(stderr, __VA_ARGS__);        \
+      fprintf(stderr, "\n");               \
+    }                                      \
+  } while (0)
+
+using Bytes = std::string;
+
+static Bytes varint(uint64_t v) {
+  Bytes o;
+  while (v >= 0x80) {
+    o.push_back((char)((v & 0x7F) | 0x80));
+    v >>= 7;
+  }
+  o.push_back((char)v);
+  return o;
+}
+static Bytes ld(int tag, const Bytes& p) { return Bytes(1, (char)tag) + varint(p.size()) + p; }
+static Bytes operation(int action, const Bytes& key, const Bytes& value, const Bytes& raw = "") {
+  return (action ? Bytes("\x08") + varint(action) : "") + ld(0x12, key) + (value.empty() ? "" : ld(0x1A, value)) + raw;
+}
+
+struct Counts {
+  uint32_t plan[3] = {0, 0, 0};
+  uint64_t calls = 0, slots = 0, bytes = 0;
+};
+
+// `lead` bytes, then the body, ending the allocation: no byte after the body is readable
+static void plan_and_encode(const Bytes& body, uint32_t k, size_t lead, Counts& cnt) {
+  const size_t n = lead + body.size();
+  uint8_t* wire = (uint8_t*)malloc(n ? n : 1);
+  memset(wire, 0x5A, lead);
+  if (body.size()) memcpy(wire + lead, body.data(), body.size());
+  const uint64_t msg_off[1] = {lead}, slot_off[1] = {0};
+  const uint32_t msg_len[1] = {(uint32_t)body.size()}, flags_off[2] = {0, k}, accept[1] = {1};
+  const uint8_t msg_status[1] = {MOCHI_MSG_OK};
+  mochi_write2_batch b;
+  memset(&b, 0, sizeof b);
+  b.n_msgs = 1;
+  b.wire = wire;
+  b.wire_len = n;
+  b.msg_off = msg_off;
+  b.msg_len = msg_len;
+  b.op_flags_off = flags_off;
+  // the store: per op a value and a certificate, in a heap blob of exactly their size
+  const Bytes value = "stored", cert = ld(0x7A, "stored-certificate");
+  const size_t store_len = (value.size() + cert.size()) * k;
+  uint8_t* store = (uint8_t*)malloc(store_len ? store_len : 1);
+  std::vector<uint8_t> dec(k), sfl(k);
+  std::vector<uint64_t> v_off(k), c_off(k);
+  std::vector<uint32_t> v_len(k), c_len(k);
+  for (uint32_t j = 0; j < k; j++) {
+    dec[j] = j % 3 == 0 ? MOCHI_OPD_APPLY : j % 3 == 1 ? MOCHI_OPD_READ : MOCHI_OPD_WRONG_SHARD;
+    sfl[j] = j % 2 ? MOCHI_W2A_HAS_STORED_CERT : 0;
+    v_off[j] = (value.size() + cert.size()) * j;
+    v_len[j] = (uint32_t)value.size();
+    c_off[j] = v_off[j] + value.size();
+    c_len[j] = (uint32_t)cert.size();
+    memcpy(store + v_off[j], value.data(), value.size());
+    memcpy(store + c_off[j], cert.data(), cert.size());
+  }
+  mochi_write2_answer_source s;
+  memset(&s, 0, sizeof s);
+  s.msg_status = msg_status;
+  s.cert_accept_bits = accept;
+  s.op_decision = dec.data();
+  s.op_value_off = v_off.data();
+  s.op_value_len = v_len.data();
+  s.op_stored_cert_off = c_off.data();
+  s.op_stored_cert_len = c_len.data();
+  s.op_store_flags = sfl.data();
+  s.store_len = store_len;
+  s.slot_off = slot_off;
+  s.n_slots = k;
+  // exactly k entries each, on the heap
+  std::vector<uint8_t> o_st(k, 0xA5), o_ex(k, 0xA5), o_fl(k, 0xA5);
+  std::vector<uint64_t> r_off(k), q_off(k);
+  std::vector<uint32_t> r_len(k), q_len(k);
+  uint8_t plan, kind;
+  uint32_t n_ops;
+  mochi_write2_answer_planned o;
+  o.plan_status = &plan;
+  o.resp_kind = &kind;
+  o.resp_n_ops = &n_ops;
+  o.op_status = o_st.data();
+  o.op_existed = o_ex.data();
+  o.op_flags = o_fl.data();
+  o.op_result_off = r_off.data();
+  o.op_result_len = r_len.data();
+  o.op_cert_off = q_off.data();
+  o.op_cert_len = q_len.data();
+  const char* err = "";
+  int rc = mochi_host::write2_answer_plan(&b, &s, &o, &err);
+  CHECK(rc == MOCHI_OK, "plan input rejected: %s", err);
+  CHECK(plan == MOCHI_W2A_REPLY || plan == MOCHI_W2A_NO_REPLY, "plan status %u", plan);
+  CHECK((plan == MOCHI_W2A_REPLY) == (kind == MOCHI_RR_WRITE2_ANS) && n_ops == (plan == MOCHI_W2A_REPLY ? k : 0u),
+        "kind %u / n_ops %u of plan status %u", kind, n_ops, plan);
+  for (uint32_t j = 0; j < k; j++) {
+    if (plan != MOCHI_W2A_REPLY) {
+      CHECK(o_st[j] == 0xFF && !o_ex[j] && !o_fl[j] && !r_len[j] && !q_len[j], "slot %u of no reply holds a value", j);
+      continue;
+    }
+    const uint64_t r_blob = o_fl[j] & MOCHI_RAO_RESULT_STORE ? store_len : n, c_blob = o_fl[j] & MOCHI_RAO_CERT_STORE ? store_len : n;
+    CHECK(r_off[j] + r_len[j] <= r_blob && q_off[j] + q_len[j] <= c_blob, "slot %u outside its blob", j);
+    if (!(o_fl[j] & (MOCHI_RAO_RESULT_STORE | MOCHI_RAO_CERT_STORE)))
+      CHECK((!r_len[j] || r_off[j] >= lead) && (!q_len[j] || q_off[j] >= lead), "slot %u before the body", j);
+  }
+  // the encoder over the plan: the size first, then into exactly that many bytes
+  mochi_result_answers a;
+  memset(&a, 0, sizeof a);
+  a.n_resps = 1;
+  a.n_slots = k;
+  a.wire = wire;
+  a.wire_len = n;
+  a.store = store;
+  a.store_len = store_len;
+  a.resp_kind = &kind;
+  a.resp_n_ops = &n_ops;
+  a.slot_off = slot_off;
+  a.op_status = o_st.data();
+  a.op_existed = o_ex.data();
+  a.op_flags = o_fl.data();
+  a.op_result_off = r_off.data();
+  a.op_result_len = r_len.data();
+  a.op_cert_off = q_off.data();
+  a.op_cert_len = q_len.data();
+  uint64_t off, need = 0, need2 = 0;
+  uint32_t len;
+  uint8_t st;
+  rc = mochi_host::result_reply_encode(&a, nullptr, 0, &off, &len, &st, &need, &err);
+  CHECK(plan == MOCHI_W2A_REPLY ? (rc == MOCHI_EINVAL && need >= 2) : (rc == MOCHI_OK && need == 0), "sizing: rc %d need %llu (%s)",
+        rc, (unsigned long long)need, err);
+  if (need) {
+    uint8_t* out = (uint8_t*)malloc(need);
+    rc = mochi_host::result_reply_encode(&a, out, need, &off, &len, &st, &need2, &err);
+    CHECK(rc == MOCHI_OK && need2 == need && len == need && st == MOCHI_ENC_OK && out[0] == 0x0A, "encode: rc %d (%s)", rc, err);
+    free(out);
+  }
+  cnt.plan[plan]++;
+  cnt.calls++;
+  cnt.slots += k;
+  cnt.bytes += need;
+  free(store);
+  free(wire);
+}
+
+int main() {
+  const Bytes cert = ld(0x0A, ld(0x0A, "server-0") + ld(0x12, ld(0x0A, ld(0x0A, "k\xc3\xa9y") + ld(0x12, Bytes("\x10\x07", 2))) +
+                                                             ld(0x22, "server-0")));
+  const Bytes groups = Bytes("\x4b\x4b\x08\x01\x4c\x4c", 6);
+  Bytes tx64;
+  for (int i = 0; i < 64; i++) tx64 += ld(0x0A, operation(i % 3, "key-" + std::to_string(i), i % 4 ? "v" + std::to_string(i) : ""));
+  struct B {
+    uint32_t k;
+    Bytes body;
+  };
+  const std::vector<B> bodies = {
+      {1, ld(0x0A, cert) + ld(0x12, ld(0x0A, operation(2, "key", "value")))},
+      {64, ld(0x0A, cert) + ld(0x12, tx64)},
+      // unknown fields and groups at all three levels, operand2 twice, the certificate after the transaction
+      {3, Bytes("\x28\x01", 2) + groups +
+              ld(0x12, ld(0x12, "\xff") + ld(0x0A, operation(2, "a", "first", ld(0x1A, "last") + groups)) + Bytes("\x08\x05", 2) +
+                           ld(0x0A, operation(1, "b", "", Bytes("\x30\x01", 2))) + groups +
+                           ld(0x0A, Bytes("\x0d\x01\x02\x03\x04", 5) + operation(2, "c", "w", ld(0x22, "\xfe")))) +
+              ld(0x32, "\xff") + ld(0x0A, cert)},
+  };
+  Counts cnt;
+  for (const B& b : bodies) {
+    for (size_t n = 0; n <= b.body.size(); n++) plan_and_encode(b.body.substr(0, n), b.k, n % 5, cnt);
+    for (size_t i = 0; i < b.body.size(); i++)
+      for (int bit = 0; bit < 8; bit++) {
+        Bytes m = b.body;
+        m[i] = (char)(m[i] ^ (1 << bit));
+        plan_and_encode(m, b.k, (i + bit) % 4, cnt);
+      }
+  }
+  plan_and_encode("", 0, 0, cnt);
+  plan_and_encode(Bytes(8, '\xff'), 2, 1, cnt);
+  CHECK(cnt.plan[MOCHI_W2A_REPLY] > 0 && cnt.plan[MOCHI_W2A_NO_REPLY] > 0, "a plan status was never reached");
+  CHECK(cnt.bytes > 0, "nothing encoded");
+  printf("result_encode_check: %llu bodies (REPLY %u, NO_REPLY %u), %llu slots, %llu bytes encoded, %d failures\n",
+         (unsigned long long)cnt.calls, cnt.plan[0], cnt.plan[1], (unsigned long long)cnt.slots, (unsigned long long)cnt.bytes,
+         g_failed);
+  return g_failed ? 1 : 0;
+}

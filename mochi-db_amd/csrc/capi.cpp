@@ -16,6 +16,7 @@
 #include "ctx.h"
 #include "mont.h"
 #include "result_decode.h"
+#include "result_encode.h"
 #include "w1_decode.h"
 #include "w1_issue.h"
 #include "w1_reply.h"
@@ -1854,6 +1855,152 @@ int mochi_result_coalesce_device(const mochi_result_tallied* t, mochi_result_coa
   int rc = check_result_tallied(t, o);
   if (rc || !t->n_reqs) return rc;
   HIP_TRY(mochi::launch_rr_coalesce(*t, *o, (hipStream_t)stream));
+  return MOCHI_OK;
+}
+
+}  // extern "C"
+
+// ---- answer encoder and Write2 answer plan (result_encode.hip / result_encode_host.cpp) ----
+namespace {
+
+int check_result_answers(const mochi_result_answers* a, const uint8_t* wire, uint64_t wire_cap, const uint64_t* msg_off,
+                         const uint32_t* msg_len, const uint8_t* status) {
+  if (!a) return fail(MOCHI_EINVAL, "null argument");
+  if (a->n_resps == 0xFFFFFFFFu) return fail(MOCHI_EINVAL, "batch too large");
+  if (!a->n_resps) return MOCHI_OK;
+  if (!a->resp_kind || !a->resp_n_ops || !a->slot_off || !msg_off || !msg_len || !status)
+    return fail(MOCHI_EINVAL, "resp_kind / resp_n_ops / slot_off / msg_off / msg_len / status required");
+  if (!a->rid_off != !a->rid_len) return fail(MOCHI_EINVAL, "rid_off and rid_len go together");
+  if (!a->nonce_off != !a->nonce_len) return fail(MOCHI_EINVAL, "nonce_off and nonce_len go together");
+  if ((a->rid_off || a->nonce_off) && a->ids_len && !a->ids) return fail(MOCHI_EINVAL, "ids required");
+  if (a->n_slots && (!a->op_status || !a->op_existed || !a->op_flags || !a->op_result_off || !a->op_result_len ||
+                     !a->op_cert_off || !a->op_cert_len))
+    return fail(MOCHI_EINVAL, "the per-slot arrays are required");
+  if (a->wire_len && !a->wire) return fail(MOCHI_EINVAL, "wire required");
+  if (a->store_len && !a->store) return fail(MOCHI_EINVAL, "store required");
+  if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire_out required");
+  return MOCHI_OK;
+}
+
+int check_write2_answer(const mochi_write2_batch* b, const mochi_write2_answer_source* s,
+                        const mochi_write2_answer_planned* o) {
+  if (!b || !s || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (b->n_msgs == 0xFFFFFFFFu) return fail(MOCHI_EINVAL, "batch too large");
+  if (!b->n_msgs) return MOCHI_OK;
+  if (!b->msg_off || !b->msg_len || !b->op_flags_off || (!b->wire && b->wire_len))
+    return fail(MOCHI_EINVAL, "wire / msg_off / msg_len / op_flags_off required");
+  if (!s->msg_status || !s->cert_accept_bits || !s->op_decision || !s->op_value_off || !s->op_value_len ||
+      !s->op_stored_cert_off || !s->op_stored_cert_len || !s->op_store_flags || !s->slot_off)
+    return fail(MOCHI_EINVAL, "every array of the answer source is required");
+  if (!o->plan_status || !o->resp_kind || !o->resp_n_ops || !o->op_status || !o->op_existed || !o->op_flags ||
+      !o->op_result_off || !o->op_result_len || !o->op_cert_off || !o->op_cert_len)
+    return fail(MOCHI_EINVAL, "every output array is required");
+  return MOCHI_OK;
+}
+
+int run_result_encode_device(mochi_ctx* c, const mochi_result_answers* in, uint8_t* wire, uint64_t wire_cap,
+                             uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                             uint64_t* wire_len_dev, hipStream_t st) {
+  const uint32_t P = in->n_resps;
+  EncState& x = c->rae;
+  if (wire_len) *wire_len = 0;
+  x.ev_valid = false;
+  if (P == 0) {
+    if (!wire_len) HIP_TRY(hipMemsetAsync(wire_len_dev, 0, 8, st));
+    return MOCHI_OK;
+  }
+  mochi::RaeArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = *in;
+  a.wire = wire;
+  a.wire_cap = wire_cap;
+  a.msg_off = msg_off;
+  a.msg_len = msg_len;
+  a.status = status;
+  int rc = x.begin(a, mochi::rae_layout, mochi::w2_small(P) ? 0 : P + 1, 8, c->profiling, mochi::kRaeEvents);
+  if (rc) return rc;
+  // the context's scratch: a call on another stream waits for the last call's kernels
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_rae_size(a, st));
+  bool fits = true;
+  uint64_t need = 0;
+  if (wire_len) {
+    if ((rc = x.fetch_totals(a.off64 + P, 8, c->ev_tot, st))) return rc;
+    *wire_len = need = *(const uint64_t*)x.tot.p;
+    fits = need <= wire_cap;
+  } else {
+    HIP_TRY(hipMemcpyAsync(wire_len_dev, a.off64 + P, 8, hipMemcpyDeviceToDevice, st));
+  }
+  if (fits) HIP_TRY(mochi::launch_rae_emit(a, st));
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(c->order.release(st));
+  return fits ? MOCHI_OK : capacity_error("wire_cap", wire_cap, "encoded size", need);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mochi_result_reply_encode_bound(uint32_t n_resps, uint64_t n_ops, uint64_t wire_len, uint64_t store_len,
+                                         uint64_t ids_len) {
+  // every op with a result and a certificate as long as the larger blob, every response with
+  // rid and nonce at ids_len, five-byte length varints and a two-byte status throughout
+  const unsigned __int128 blob = wire_len > store_len ? wire_len : store_len;
+  unsigned __int128 t = (unsigned __int128)n_ops * (2 * blob + 24) + (unsigned __int128)n_resps * (2 * (unsigned __int128)ids_len + 18);
+  const unsigned __int128 cap = (unsigned __int128)n_resps * mochi::kEncMaxMsg;  // longer bodies are emitted empty
+  if (t > cap) t = cap;
+  return (uint64_t)t;
+}
+
+int mochi_result_reply_encode(const mochi_result_answers* a, uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off,
+                              uint32_t* msg_len, uint8_t* status, uint64_t* wire_len) {
+  if (!wire_len) return fail(MOCHI_EINVAL, "wire_len required");
+  *wire_len = 0;
+  int rc = check_result_answers(a, wire, wire_cap, msg_off, msg_len, status);
+  if (rc || !a->n_resps) return rc;
+  const char* err = "";
+  rc = mochi_host::result_reply_encode(a, wire, wire_cap, msg_off, msg_len, status, wire_len, &err);
+  return rc ? fail(rc, "mochi_result_reply_encode: %s", err) : MOCHI_OK;
+}
+
+int mochi_result_reply_encode_device(mochi_ctx* c, const mochi_result_answers* a, uint8_t* wire, uint64_t wire_cap,
+                                     uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                                     uint64_t* wire_len_dev, void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  if (!wire_len && !wire_len_dev) return fail(MOCHI_EINVAL, "wire_len or wire_len_dev required");
+  int rc = check_result_answers(a, wire, wire_cap, msg_off, msg_len, status);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  return run_result_encode_device(c, a, wire, wire_cap, msg_off, msg_len, status, wire_len, wire_len_dev,
+                                  (hipStream_t)stream);
+}
+
+int mochi_ctx_read_result_encode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n_kernels) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  static const int kSpan[mochi::kRaeStages][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+  return c->rae.read_profile(kSpan, mochi::kRaeStages, kernel_ms, n_kernels,
+                             "no answer encode call was made while profiling was on");
+}
+
+int mochi_write2_answer_plan(const mochi_write2_batch* b, const mochi_write2_answer_source* s,
+                             mochi_write2_answer_planned* o) {
+  int rc = check_write2_answer(b, s, o);
+  if (rc || !b->n_msgs) return rc;
+  const char* err = "";
+  rc = mochi_host::write2_answer_plan(b, s, o, &err);
+  return rc ? fail(rc, "mochi_write2_answer_plan: %s", err) : MOCHI_OK;
+}
+
+int mochi_write2_answer_plan_device(const mochi_write2_batch* b, const mochi_write2_answer_source* s,
+                                    mochi_write2_answer_planned* o, void* stream) {
+  int rc = check_write2_answer(b, s, o);
+  if (rc || !b->n_msgs) return rc;
+  const mochi::rae::PlanView v{*b, *s, *o};
+  HIP_TRY(mochi::launch_w2a_plan(v, (hipStream_t)stream));
   return MOCHI_OK;
 }
 

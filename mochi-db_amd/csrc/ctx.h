@@ -62,7 +62,7 @@ struct PinnedBuf {
   }
 };
 
-// What one wire encoder (w2_encode.hip, w1_issue.hip, w1_reply.hip) keeps between calls.
+// What one wire encoder (w2_encode.hip, w1_issue.hip, w1_reply.hip, result_encode.hip) keeps between calls.
 struct EncState {
   DevBuf scratch, scan;        // per-call scratch; temp of the device-wide scan
   PinnedBuf tot;               // the totals the host waits for
@@ -203,6 +203,7 @@ struct mochi_ctx {
   mochi::EncState w1d;  // Write1 reply decoder (w1_decode.hip); its totals are the grant and certificate counts
   mochi::DevBuf w1d_sig;  // ... and its signature sources, sized once the grant total is known
   mochi::EncState rr;   // result reply decoder (result_decode.hip); it waits for no total
+  mochi::EncState rae;  // answer encoder (result_encode.hip); its total is the wire size
   // the last host-path call's certificate accept bitmap on the device (a slice
   // of dev_out, valid until the next call on this context; nullptr when the
   // device copy is not the final verdict, e.g. after host fallback decisions):

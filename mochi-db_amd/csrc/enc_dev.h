@@ -1,5 +1,5 @@
 // enc_dev.h — device helpers shared by the wire encoders (w2_encode.hip,
-// w1_issue.hip, w1_reply.hip): short header runs gathered into dword stores
+// w1_issue.hip, w1_reply.hip, result_encode.hip): short header runs gathered into dword stores
 // (Put), payload copies by aligned 16-byte destination chunks (copy_chunk,
 // copy_run) and the end of a size kernel (enc_place).
 #pragma once

@@ -1,5 +1,5 @@
 // enc_launch.h — host-side launch helpers shared by the wire encoders
-// (w2_encode.hip, w1_issue.hip, w1_reply.hip): grid arithmetic, the scratch
+// (w2_encode.hip, w1_issue.hip, w1_reply.hip, result_encode.hip): grid arithmetic, the scratch
 // layout cursor (carve.h), the per-kernel profiling stamps and the 64-bit hipcub scans.
 #pragma once
 #include <hip/hip_runtime.h>

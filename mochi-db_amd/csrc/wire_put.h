@@ -1,5 +1,5 @@
 // wire_put.h — protobuf byte writers and the bounds predicate of the encoders'
-// host twins (w2_encode_host.cpp, w1_issue_host.cpp, w1_reply_host.cpp).
+// host twins (w2_encode_host.cpp, w1_issue_host.cpp, w1_reply_host.cpp, result_encode_host.cpp).
 #pragma once
 #include <cstdint>
 #include <cstring>

@@ -222,6 +222,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_ctx_read_result_decode_profile.argtypes = [vp, vp, u32]
     lib.mochi_result_coalesce.argtypes = [vp, vp]
     lib.mochi_result_coalesce_device.argtypes = [vp, vp, vp]
+    lib.mochi_result_reply_encode_bound.restype = u64
+    lib.mochi_result_reply_encode_bound.argtypes = [u32, u64, u64, u64, u64]
+    lib.mochi_result_reply_encode.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+    lib.mochi_result_reply_encode_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.mochi_ctx_read_result_encode_profile.argtypes = [vp, vp, u32]
+    lib.mochi_write2_answer_plan.argtypes = [vp, vp, vp]
+    lib.mochi_write2_answer_plan_device.argtypes = [vp, vp, vp, vp]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -609,6 +616,33 @@ class Verifier:
         if self.lib.mochi_ctx_read_result_decode_profile(self.ctx, _ptr(ms), ms.size) != OK:
             raise MochiError(f"mochi_ctx_read_result_decode_profile: {_err(self.lib)}")
         return dict(zip(RESULT_DECODE_STAGES, (float(x) for x in ms)))
+
+    def result_reply_encode_device(self, danswers: "DeviceResultAnswers", wire, msg_off, msg_len, status,
+                                   stream: int = 0, wire_len_dev=None, check: bool = True):
+        """mochi_result_reply_encode_device: the Write2 / read answer bodies of `danswers` into
+        the uint8 tensor `wire` (None = capacity 0), msg_off (int64) / msg_len (int32) / status
+        (uint8) [P] on the device.  wire_len_dev None: the call waits for the total; returns
+        (rc, total), rc EINVAL when the total exceeds the capacity (raises then if `check`).
+        wire_len_dev an int64 tensor of one element: no host wait, the total goes there and
+        nothing is written to `wire` when it exceeds the capacity; returns (rc, None)."""
+        a = danswers.to_c()
+        cap = 0 if wire is None else int(wire.numel())
+        need = ctypes.c_uint64(0)
+        rc = self.lib.mochi_result_reply_encode_device(
+            self.ctx, ctypes.addressof(a), wire.data_ptr() if cap else None, cap, msg_off.data_ptr(),
+            msg_len.data_ptr(), status.data_ptr(), ctypes.addressof(need) if wire_len_dev is None else None,
+            None if wire_len_dev is None else wire_len_dev.data_ptr(), stream or None)
+        short = wire_len_dev is None and rc == EINVAL and int(need.value) > cap
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_result_reply_encode_device rc={rc}: {_err(self.lib)}")
+        return rc, (int(need.value) if wire_len_dev is None else None)
+
+    def read_result_encode_profile(self) -> dict:
+        """Per-kernel ms of the last result_reply_encode_device call made with set_profiling(True)."""
+        ms = np.zeros(len(RESULT_ENCODE_STAGES), np.float32)
+        if self.lib.mochi_ctx_read_result_encode_profile(self.ctx, _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_result_encode_profile: {_err(self.lib)}")
+        return dict(zip(RESULT_ENCODE_STAGES, (float(x) for x in ms)))
 
     def decode_write2(self, wb) -> dict:
         """The device decoder's SoA view of the messages (inspection / tests)."""
@@ -2592,6 +2626,281 @@ def result_coalesce_device(dreplies: "DeviceResultReplies", decoded: "DeviceResu
     rc = lib.mochi_result_coalesce_device(ctypes.addressof(t), ctypes.addressof(o), stream or None)
     if rc != OK:
         raise MochiError(f"mochi_result_coalesce_device rc={rc}: {_err(lib)}")
+
+
+# ---------------------------------------------------------------------------
+# Answer encode (the server's closing round): caller arrays -> Write2AnsFromServer /
+# ReadFromServer bodies, the inverse of result_reply_decode; and the plan that fills those
+# arrays from the Write2 verifier's outputs
+# ---------------------------------------------------------------------------
+ENC_BAD_OP = 4
+RAO_HAS_CERT, RAO_RESULT_STORE, RAO_CERT_STORE = 0x01, 0x02, 0x04
+W2A_REPLY, W2A_NO_REPLY, W2A_HOST = range(3)
+W2A_HAS_STORED_CERT, W2A_VALUE_NULL = 0x01, 0x02
+RESULT_ENCODE_STAGES = ("k_rae_size", "scan", "k_rae_hdr", "k_rae_copy")
+
+# the arrays of mochi_result_answers: "P" per response, "S" per slot, "B" a blob; "?" may be None
+_RA_IN = dict(wire=(np.uint8, "B"), store=(np.uint8, "B"), ids=(np.uint8, "B"), resp_kind=(np.uint8, "P"),
+              resp_n_ops=(np.uint32, "P"), slot_off=(np.uint64, "P"), rid_off=(np.uint64, "P?"),
+              rid_len=(np.uint32, "P?"), nonce_off=(np.uint64, "P?"), nonce_len=(np.uint32, "P?"),
+              op_status=(np.uint8, "S"), op_existed=(np.uint8, "S"), op_flags=(np.uint8, "S"),
+              op_result_off=(np.uint64, "S"), op_result_len=(np.uint32, "S"), op_cert_off=(np.uint64, "S"),
+              op_cert_len=(np.uint32, "S"))
+_RA_SLOT = tuple(k for k, (dt, w) in _RA_IN.items() if w == "S")
+# the outputs of the Write2 answer plan: "M" per message, "S" per slot
+_W2A_OUT = dict(plan_status=(np.uint8, "M"), resp_kind=(np.uint8, "M"), resp_n_ops=(np.uint32, "M"),
+                **{k: _RA_IN[k] for k in _RA_SLOT})
+# the per-op arrays of mochi_write2_answer_source the store supplies
+_W2A_STORE = dict(op_value_off=np.uint64, op_value_len=np.uint32, op_stored_cert_off=np.uint64,
+                  op_stored_cert_len=np.uint32, op_store_flags=np.uint8)
+
+
+class ResultAnswers_C(ctypes.Structure):
+    _fields_ = [("n_resps", ctypes.c_uint32), ("n_slots", ctypes.c_uint32), ("wire", ctypes.c_void_p),
+                ("wire_len", ctypes.c_uint64), ("store", ctypes.c_void_p), ("store_len", ctypes.c_uint64),
+                ("ids", ctypes.c_void_p), ("ids_len", ctypes.c_uint64)] + \
+        [(k, ctypes.c_void_p) for k, (dt, w) in _RA_IN.items() if w != "B"]
+
+
+class Write2AnswerSource_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("msg_status", "cert_accept_bits", "op_decision") + tuple(_W2A_STORE)] + \
+        [("store_len", ctypes.c_uint64), ("slot_off", ctypes.c_void_p), ("n_slots", ctypes.c_uint32),
+         ("_pad0", ctypes.c_uint32)]
+
+
+class Write2AnswerPlanned_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _W2A_OUT]
+
+
+@dataclass
+class ResultAnswers:
+    """What a server answers in the closing round (mochi_result_answers, host arrays).  The
+    per-slot arrays all have one length, n_slots."""
+
+    wire: np.ndarray  # uint8: the received request bytes
+    store: np.ndarray  # uint8: stored values and certificates
+    ids: np.ndarray  # uint8: rid and nonce strings
+    resp_kind: np.ndarray  # uint8 [P] RR_*
+    resp_n_ops: np.ndarray  # uint32 [P]
+    slot_off: np.ndarray  # uint64 [P]
+    rid_off: Optional[np.ndarray]  # uint64 [P] or None = every rid empty
+    rid_len: Optional[np.ndarray]  # uint32 [P]
+    nonce_off: Optional[np.ndarray]  # uint64 [P] or None = every nonce empty
+    nonce_len: Optional[np.ndarray]  # uint32 [P]
+    op_status: np.ndarray  # uint8 [S]
+    op_existed: np.ndarray  # uint8 [S]
+    op_flags: np.ndarray  # uint8 [S] RAO_*
+    op_result_off: np.ndarray  # uint64 [S]
+    op_result_len: np.ndarray  # uint32 [S]
+    op_cert_off: np.ndarray  # uint64 [S]
+    op_cert_len: np.ndarray  # uint32 [S]
+
+    @property
+    def n_resps(self) -> int:
+        return int(np.asarray(self.resp_kind).shape[0])
+
+    @property
+    def n_slots(self) -> int:
+        return int(np.asarray(self.op_status).shape[0])
+
+    @property
+    def n_ops(self) -> int:
+        return int(np.asarray(self.resp_n_ops, np.uint64).sum())
+
+    def arrays(self) -> dict:
+        """Every given array C-contiguous in its ABI dtype (None stays None)."""
+        return {k: None if getattr(self, k) is None else np.ascontiguousarray(getattr(self, k), dt).reshape(-1)
+                for k, (dt, w) in _RA_IN.items()}
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = ResultAnswers_C()
+        c.n_resps, c.n_slots = self.n_resps, self.n_slots
+        c.wire_len, c.store_len, c.ids_len = (int(arrs[k].size) for k in ("wire", "store", "ids"))
+        for k, a in arrs.items():
+            if a is not None and a.size == 0:  # an empty array still gets a valid address
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def result_reply_encode_bound(answers) -> int:
+    """mochi_result_reply_encode_bound for a ResultAnswers or a DeviceResultAnswers."""
+    size = lambda k: int(getattr(answers, k + "_len")) if hasattr(answers, k + "_len") else int(np.asarray(getattr(answers, k)).size)
+    return int(load_library().mochi_result_reply_encode_bound(answers.n_resps, answers.n_ops, size("wire"), size("store"),
+                                                              size("ids")))
+
+
+def result_reply_encode_into(answers: "ResultAnswers", wire: Optional[np.ndarray]):
+    """mochi_result_reply_encode into the caller's buffer (uint8; None = capacity 0).
+    Returns (rc, wire_len, msg_off, msg_len, status); rc is EINVAL with wire_len = the size
+    needed when the buffer is too small (no byte of it written); any other failure raises."""
+    lib = load_library()
+    a, keep = answers.to_c()
+    P = answers.n_resps
+    off, ln, st = np.zeros(max(P, 1), np.uint64), np.zeros(max(P, 1), np.uint32), np.zeros(max(P, 1), np.uint8)
+    cap = 0 if wire is None else int(wire.nbytes)
+    need = ctypes.c_uint64(0)
+    rc = lib.mochi_result_reply_encode(ctypes.addressof(a), _ptr(wire) if cap else None, cap, _ptr(off), _ptr(ln),
+                                       _ptr(st), ctypes.addressof(need))
+    if rc != OK and not (rc == EINVAL and int(need.value) > cap):
+        raise MochiError(f"mochi_result_reply_encode rc={rc}: {_err(lib)}")
+    return rc, int(need.value), off[:P], ln[:P], st[:P]
+
+
+def result_reply_encode(answers: "ResultAnswers"):
+    """Host form of the answer encoder: sizes first, then the bodies into a buffer of exactly
+    the size needed.  Returns (wire, msg_off, msg_len, status)."""
+    rc, need, off, ln, st = result_reply_encode_into(answers, None)
+    wire = np.zeros(need, np.uint8)
+    if need:
+        rc, need, off, ln, st = result_reply_encode_into(answers, wire)
+    assert rc == OK
+    return wire, off, ln, st
+
+
+class DeviceResultAnswers:
+    """A ResultAnswers in device memory (plumbing only): copied with torch, or built from
+    tensors that are already there (uint32 as int32, uint64 as int64)."""
+
+    def __init__(self, answers: "ResultAnswers", device: int = 0):
+        self.n_resps, self.n_slots, self.n_ops = answers.n_resps, answers.n_slots, answers.n_ops
+        for k, a in answers.arrays().items():
+            if _RA_IN[k][1] == "B":
+                setattr(self, k + "_len", int(a.size))
+            setattr(self, k, None if a is None else _to_dev(a, device))
+
+    @classmethod
+    def from_tensors(cls, n_resps: int, n_slots: int, n_ops: int, **tensors) -> "DeviceResultAnswers":
+        """n_ops: the sum of resp_n_ops or a bound on it (read by result_reply_encode_bound alone)."""
+        self = cls.__new__(cls)
+        self.n_resps, self.n_slots, self.n_ops = int(n_resps), int(n_slots), int(n_ops)
+        for k, (dt, w) in _RA_IN.items():
+            t = tensors.get(k)
+            setattr(self, k, t)
+            if w == "B":
+                setattr(self, k + "_len", 0 if t is None else int(t.numel()))
+        return self
+
+    def to_c(self) -> ResultAnswers_C:
+        c = ResultAnswers_C()
+        c.n_resps, c.n_slots = self.n_resps, self.n_slots
+        c.wire_len, c.store_len, c.ids_len = self.wire_len, self.store_len, self.ids_len
+        for k in _RA_IN:
+            t = getattr(self, k)
+            setattr(c, k, None if t is None else t.data_ptr())
+        return c
+
+
+@dataclass
+class Write2AnswerStore:
+    """The store's side of a Write2 batch's ops (host arrays, aligned with op_flags_off), the
+    blob they point into, and where each message's slots start."""
+
+    store: np.ndarray  # uint8
+    op_value_off: np.ndarray  # uint64 [O]
+    op_value_len: np.ndarray  # uint32 [O]
+    op_stored_cert_off: np.ndarray  # uint64 [O]
+    op_stored_cert_len: np.ndarray  # uint32 [O]
+    op_store_flags: np.ndarray  # uint8 [O] W2A_*
+    slot_off: np.ndarray  # uint64 [M]
+    n_slots: int
+
+    def arrays(self) -> dict:
+        d = {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in _W2A_STORE.items()}
+        d["slot_off"] = np.ascontiguousarray(self.slot_off, np.uint64).reshape(-1)
+        d["store"] = np.ascontiguousarray(self.store, np.uint8).reshape(-1)
+        return d
+
+
+def write2_answer_plan(wb, msg_status, cert_accept_bits, op_decision, st: "Write2AnswerStore", fill: int = 0) -> dict:
+    """mochi_write2_answer_plan (host form) for a workload.WireBatch and the verify call's
+    outputs: the arrays of mochi_write2_answer_planned by name, over buffers prefilled with `fill`."""
+    lib = load_library()
+    b, keep = write2_batch_c(wb)
+    some = lambda a, dt: np.ascontiguousarray(a if np.asarray(a).size else np.zeros(1, dt), dt).reshape(-1)
+    ins = dict(msg_status=some(msg_status, np.uint8), cert_accept_bits=some(cert_accept_bits, np.uint32),
+               op_decision=some(op_decision, np.uint8))
+    arrs = st.arrays()
+    s = Write2AnswerSource_C()
+    for k, a in ins.items():
+        setattr(s, k, _ptr(a))
+    for k in tuple(_W2A_STORE) + ("slot_off",):
+        arrs[k] = arrs[k] if arrs[k].size else np.zeros(1, arrs[k].dtype)
+        setattr(s, k, _ptr(arrs[k]))
+    s.store_len, s.n_slots = int(arrs["store"].size), int(st.n_slots)
+    n = dict(M=int(b.n_msgs), S=int(st.n_slots))
+    out = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _W2A_OUT.items()}
+    o = Write2AnswerPlanned_C()
+    for k, a in out.items():
+        setattr(o, k, _ptr(a if a.size else np.zeros(1, a.dtype)))
+    rc = lib.mochi_write2_answer_plan(ctypes.addressof(b), ctypes.addressof(s), ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_write2_answer_plan rc={rc}: {_err(lib)}")
+    return out
+
+
+def planned_answers(wire, store, ids, planned: dict, slot_off, rid_off=None, rid_len=None) -> "ResultAnswers":
+    """The plan's outputs as the encoder's input (host arrays)."""
+    return ResultAnswers(wire=wire, store=store, ids=ids, resp_kind=planned["resp_kind"],
+                         resp_n_ops=planned["resp_n_ops"], slot_off=slot_off, rid_off=rid_off, rid_len=rid_len,
+                         nonce_off=None, nonce_len=None, **{k: planned[k] for k in _RA_SLOT})
+
+
+class DeviceWrite2AnswerStore:
+    """A Write2AnswerStore copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, st: "Write2AnswerStore", device: int = 0):
+        self.n_slots = int(st.n_slots)
+        for k, a in st.arrays().items():
+            if k == "store":
+                self.store_len = int(a.size)
+            setattr(self, k, _to_dev(a, device))
+
+
+class DeviceWrite2AnswerPlanned:
+    """Device buffers for the outputs of write2_answer_plan_device, prefilled with `fill`."""
+
+    def __init__(self, n_msgs: int, n_slots: int, device: int = 0, fill: int = 0):
+        self.n = dict(M=int(n_msgs), S=int(n_slots))
+        for k, (dt, w) in _W2A_OUT.items():
+            setattr(self, k, _dev_full(self.n[w], dt, fill, device))
+
+    def to_c(self) -> Write2AnswerPlanned_C:
+        o = Write2AnswerPlanned_C()
+        for k in _W2A_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        return o
+
+    def to_host(self) -> dict:
+        return {k: getattr(self, k).cpu().numpy().view(dt)[:self.n[w]] for k, (dt, w) in _W2A_OUT.items()}
+
+    def answers(self, dwb: "DeviceWireBatch", dst: "DeviceWrite2AnswerStore", ids=None, rid_off=None,
+                rid_len=None) -> "DeviceResultAnswers":
+        """The encoder's input over these buffers: no copy, no host round trip."""
+        return DeviceResultAnswers.from_tensors(
+            self.n["M"], self.n["S"], self.n["S"], wire=dwb.wire, store=dst.store, ids=ids, resp_kind=self.resp_kind,
+            resp_n_ops=self.resp_n_ops, slot_off=dst.slot_off, rid_off=rid_off, rid_len=rid_len,
+            **{k: getattr(self, k) for k in _RA_SLOT})
+
+
+def write2_answer_plan_device(dwb: "DeviceWireBatch", verdicts: "DeviceVerdicts", dst: "DeviceWrite2AnswerStore",
+                              out: "DeviceWrite2AnswerPlanned", stream: int = 0) -> None:
+    """mochi_write2_answer_plan_device: one kernel on `stream`, no wait.  Reads dwb.status,
+    verdicts.cert_accept_bits and verdicts.op_decision in stream order: it may be enqueued
+    right behind Verifier.verify_write2_device."""
+    lib = load_library()
+    b = dwb.to_c()
+    s = Write2AnswerSource_C()
+    s.msg_status, s.cert_accept_bits = dwb.status.data_ptr(), verdicts.cert_accept_bits.data_ptr()
+    s.op_decision = verdicts.op_decision.data_ptr()
+    for k in tuple(_W2A_STORE) + ("slot_off",):
+        setattr(s, k, getattr(dst, k).data_ptr())
+    s.store_len, s.n_slots = dst.store_len, dst.n_slots
+    o = out.to_c()
+    rc = lib.mochi_write2_answer_plan_device(ctypes.addressof(b), ctypes.addressof(s), ctypes.addressof(o), stream or None)
+    if rc != OK:
+        raise MochiError(f"mochi_write2_answer_plan_device rc={rc}: {_err(lib)}")
 
 
 # ---------------------------------------------------------------------------
