@@ -38,6 +38,13 @@ the way the reference's threads can.  Java collection orders that reach the
 wire are reproduced: HashSet<Server> send order, HashMap<String,...> iteration
 order of the certificate and grant maps (MochiDBClient.java:291-299, 333-338;
 InMemoryDataStore.java:283-295).
+
+Seams for tests/wire_cluster.py (the same cluster with every message as protobuf
+bytes) and for scripted scenarios: `seed_hook` forces a request's seed,
+`resend_write1` sends a Write1 again, `step(deliveries=...)` delivers exactly the
+given (request, server) pairs, and the `_on_*` / `_finish_*` / `_write2_body` /
+`_merged_result` methods are where a subclass handles a step's deliveries per
+server as one batch.  None of them draws from the scheduler's generator.
 """
 from __future__ import annotations
 
@@ -188,6 +195,7 @@ class OpResult:
     result: str = ""
     existed: bool = False
     cert: Optional[Cert] = None
+    cert_bytes: Optional[bytes] = field(default=None, compare=False)  # wire backends: the certificate as received
 
 
 # ---------------------------------------------------------------------------
@@ -374,6 +382,7 @@ class Pending:
     dead: set = field(default_factory=set)  # servers that threw (no reply)
     t_start: float = 0.0
     outstanding: int = 0  # async Write2s delivered but not yet applied (async_w2 mode)
+    wire: Dict[int, object] = field(default_factory=dict)  # wire backends: the reply bodies, per server
 
 
 @dataclass
@@ -389,6 +398,8 @@ class AsyncW2:
 
 
 class Cluster:
+    wire = False  # True in tests/wire_cluster.py: every message between client and server is protobuf bytes
+
     def __init__(self, backend: str = "device", check_oracle: bool = False, seed: int = 1, device: int = 0,
                  config_path: str = SAMPLE_CONFIG, key_dir: str = W.DEFAULT_KEY_DIR, max_wait_us: int = 200,
                  async_w2: bool = False, p_apply: float = 0.35):
@@ -438,7 +449,9 @@ class Cluster:
         self.inflight: List[Pending] = []
         self.n_clients = 0
         self.stats = {"write1": 0, "write2": 0, "reads": 0, "retries": 0, "oracle_checked": 0, "steps": 0,
-                      "signed": 0, "read_branch": 0, "resubmits": 0, "max_same_key_inflight": 0}
+                      "signed": 0, "read_branch": 0, "resubmits": 0, "max_same_key_inflight": 0,
+                      "w1_refused": 0, "w1_refused_in_batch": 0, "w1_refused_stored": 0, "w1_from_stored": 0}
+        self.seed_hook = None  # (Pending, drawn seed) -> the seed to send (the draw is made either way)
         self.config_path = config_path
 
     def close(self):
@@ -624,28 +637,74 @@ class Cluster:
     def _send_write1(self, p: Pending):
         p.kind = "W1"
         p.seed = self.rng.randrange(1000)  # Random.nextInt(1000) (MochiDBClient.java:262)
+        if self.seed_hook is not None:
+            p.seed = self.seed_hook(p, p.seed)
         p.todo = list(self.send_order)
         p.replies = {}
+        p.wire = {}
         self.inflight.append(p)
         self.stats["write1"] += 1
 
+    def resend_write1(self, p: Pending, s: int):
+        """The same Write1 (same hash, same seed) goes to server s once more."""
+        assert p.kind == "W1" and s not in p.todo
+        p.todo.append(s)
+
+    # --- seams the wire backends (tests/wire_cluster.py) override ---------------------
+    def _client_id(self, p: Pending) -> str:
+        return ""
+
+    def _on_write1(self, srv: Server, p: Pending, kind: str, mg: MultiGrantRec, new: List[GrantRec]):
+        pass
+
+    def _finish_write1(self, w1_new: Dict[int, List[GrantRec]]):
+        for s, grants in w1_new.items():  # the Write1 site signs every grant it issues
+            self._sign(self.servers[s], grants)
+
+    def _on_read(self, srv: Server, p: Pending, res):
+        pass
+
+    def _finish_reads(self):
+        pass
+
+    def _write2_body(self, p: Pending) -> bytes:
+        wc = b"".join(W.encode_map_entry(1, sid.encode(), mg.encode()) for sid, mg in p.cert.mgs)
+        return W._ld(1, wc) + W._ld(2, encode_txn(p.ops))
+
+    def _merged_result(self, p: Pending, resps, ch, n: int) -> List[OpResult]:
+        """The client's result of tally n of this step: per op the chosen server's."""
+        return [resps[int(ch[i])][i] for i in range(len(p.ops))]
+
+    def _count_write1(self, s: int, kind: str, mg: MultiGrantRec, new: List[GrantRec], step_new: List[GrantRec]):
+        """Where the reply's grants came from: a grant of this step (the same batch) or a stored one."""
+        old = [g for g in mg.grants if not any(g is n for n in new)]
+        in_batch = any(g is n for g in old for n in step_new)
+        if kind == "REFUSED":
+            self.stats["w1_refused"] += 1
+            self.stats["w1_refused_in_batch" if in_batch else "w1_refused_stored"] += 1
+        elif old and not in_batch:
+            self.stats["w1_from_stored"] += 1
+
     # --- the scheduler ---------------------------------------------------------------
-    def step(self, p_deliver: float = 0.6):
+    def step(self, p_deliver: float = 0.6, deliveries=None):
         """Deliver a random subset of the in-flight messages, run the library on
         the batch they form, and advance the clients whose rounds completed.
         Returns the list of (Pending, outcome) finished this step, outcome =
         list of OpResult or a ClientError."""
         self.stats["steps"] += 1
-        deliveries = []
-        for p in self.inflight:
-            for s in list(p.todo):
-                if self.rng.random() < p_deliver:
-                    deliveries.append((p, s))
-        if not deliveries:  # always make progress
-            p = next((q for q in self.inflight if q.todo), None)
-            if p is not None:
-                deliveries.append((p, p.todo[0]))
-        self.rng.shuffle(deliveries)
+        if deliveries is None:
+            deliveries = []
+            for p in self.inflight:
+                for s in list(p.todo):
+                    if self.rng.random() < p_deliver:
+                        deliveries.append((p, s))
+            if not deliveries:  # always make progress
+                p = next((q for q in self.inflight if q.todo), None)
+                if p is not None:
+                    deliveries.append((p, p.todo[0]))
+            self.rng.shuffle(deliveries)
+        else:  # a scripted step: exactly these (Pending, server) pairs, in this order, no draw
+            deliveries = list(deliveries)
         # one Write2 per (server, key) per step (the object's write lock serialises them)
         locked = set()
         w1_new: Dict[int, List[GrantRec]] = {}
@@ -670,8 +729,10 @@ class Cluster:
             elif p.kind == "W1":
                 if any((s, op.key) in locked for op in p.ops):
                     continue
-                kind, mg, new = srv.write1(p.ops, p.seed, p.thash, "")
+                kind, mg, new = srv.write1(p.ops, p.seed, p.thash, self._client_id(p))
+                self._count_write1(s, kind, mg, new, w1_new.get(s, []))
                 w1_new.setdefault(s, []).extend(new)
+                self._on_write1(srv, p, kind, mg, new)
                 p.replies[s] = (kind, mg)
                 self.log.append((s, "W1", p, (kind, [(g.object_id, g.ts, g.txn_hash, g.status) for g in mg.grants],
                                             p.seed)))
@@ -680,13 +741,14 @@ class Cluster:
                     continue
                 res = srv.read(p.ops)
                 self.log.append((s, "R", p, res))
+                self._on_read(srv, p, res)
                 if res is None:
                     p.dead.add(s)
                 else:
                     p.replies[s] = res
             p.todo.remove(s)
-        for s, grants in w1_new.items():  # the Write1 site signs every grant it issues
-            self._sign(self.servers[s], grants)
+        self._finish_write1(w1_new)
+        self._finish_reads()
         for (srv, p, flags, ots), v in zip(w2_jobs, self._verify_write2(w2_jobs)):
             self._apply_w2(srv, p, v)
         if self.async_w2:
@@ -725,8 +787,7 @@ class Cluster:
                     order = java_hash_order([mg.server_id for _, mg in resps],
                                             [java_string_hash(mg.server_id) for _, mg in resps])
                     p.cert = Cert([(sid, by_id[sid]) for sid in order])
-                    wc = b"".join(W.encode_map_entry(1, sid.encode(), mg.encode()) for sid, mg in p.cert.mgs)
-                    p.msg = W._ld(1, wc) + W._ld(2, encode_txn(p.ops))
+                    p.msg = self._write2_body(p)
                     p.kind = "W2"
                     p.todo = list(self.send_order)
                     p.replies = {}
@@ -737,11 +798,11 @@ class Cluster:
                     finished.append((p, RequestFailed(f"Write1 decision {int(dec)}")))
         if tallies:
             acc, chosen = self._tally(tallies)
-            for (p, resps), a, ch in zip(tallies, acc, chosen):
+            for n, ((p, resps), a, ch) in enumerate(zip(tallies, acc, chosen)):
                 if not a:
                     finished.append((p, InconsistentWrite() if p.kind == "W2" else InconsistentRead()))
                     continue
-                res = [resps[int(ch[i])][i] for i in range(len(p.ops))]
+                res = self._merged_result(p, resps, ch, n)
                 if any(r.status == ST_WRONG_SHARD for r in res):  # validateThatAllResponsesAreOk (:91-100)
                     finished.append((p, ClientError("wrong shard in merged result")))
                 else:
