@@ -552,6 +552,8 @@ enum mochi_enc_status {
   MOCHI_ENC_TOO_LONG = 3,   /* the message would be 2^31 bytes or more              */
   MOCHI_ENC_BAD_OP = 4,     /* answer encoder alone: an op slot of the response reads absent
                                (op_status 0xFF); the response's size is then not computed    */
+  MOCHI_ENC_BAD_KIND = 5,   /* envelope encoder alone (device form): a kind above 12        */
+  MOCHI_ENC_BAD_ID = 6,     /* envelope encoder alone (device form): an id that is not UTF-8 */
 };
 
 /* A safe upper bound on the wire size, from the counts and the two blob
@@ -1456,6 +1458,222 @@ int mochi_write2_answer_plan(const mochi_write2_batch* batch, const mochi_write2
  * are trusted, the bytes of `wire` are not. */
 int mochi_write2_answer_plan_device(const mochi_write2_batch* batch, const mochi_write2_answer_source* src,
                                     mochi_write2_answer_planned* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The ProtocolMessage ENVELOPE (MochiProtocol.proto:194-213, one frame of
+ * MochiServerInitializer.java:30-33 with Netty's length prefix stripped):
+ *
+ *   ProtocolMessage = [28 msgTimestamp] [32 serverId] [3A msgId] [42 replyToMsgId]
+ *                     [payload: one of the fields 101..112, length-delimited]
+ *
+ * Four calls, each in a host form (no GPU, no context) and a device form:
+ * decode (frames -> status, payload case, body slice, the four scalars), route
+ * (the server's side: a stable partition of the OK frames by payload case, whose
+ * runs are the msg_off / msg_len of the body decoders), join (the client's side:
+ * replies matched to the outstanding requests by replyToMsgId, grouped by
+ * request: the resp_off / resp_len / resp_kind / req_resp_off of the reply
+ * decoders) and encode (bodies wrapped into frames, the inverse of decode).
+ * What stays with the caller: msgId generation (UUIDs), sockets and cutting the
+ * byte stream into frames.
+ *
+ * Frame f is wire[frame_off[f], +frame_len[f]): any alignment, slices may alias,
+ * at most 2^24 frames.  The bytes are an untrusted peer's: every read stays
+ * inside the frame's slice; the caller's own offsets are trusted (the host form
+ * checks them against wire_len).  Parsing is protobuf-java 3.16.3's, as in the
+ * body decoders: singular fields last-wins; unknown fields and known field
+ * numbers with a foreign wire type are skipped (a payload field that is not
+ * length-delimited included), groups to depth 100; field number 0 or a bad
+ * varint is malformed; overlong varint tags are accepted; msgTimestamp is the
+ * low 64 bits of its varint; serverId, msgId and replyToMsgId are strict UTF-8,
+ * every occurrence of them.
+ *
+ * Status per frame:
+ *   MOCHI_ENV_OK         the envelope level parses and holds at most one
+ *     length-delimited field among 101..112.
+ *   MOCHI_ENV_MALFORMED  protobuf-java throws on the envelope level itself
+ *     (framing, a string that is not UTF-8), whatever the payloads are.
+ *   MOCHI_ENV_FALLBACK   the envelope level parses, validated whole, and holds
+ *     more than one length-delimited field among 101..112.  The generated parser
+ *     parses every payload field it meets, merges when the case repeats and
+ *     replaces when it changes: such a frame is either a merge, where no single
+ *     slice is the value, or has a discarded body that Java still parsed and could
+ *     have thrown on.  It is never MALFORMED on account of a body, and it is
+ *     not decoded: the caller hands it to protobuf-java.  No canonical writer
+ *     produces one.
+ * Contract against the body decoders: Java throws on a frame exactly when the
+ * envelope is MALFORMED, or it is OK and the decoder of its kind calls the body
+ * MALFORMED.  The bodies of kinds 1-4 (the Hello messages) and 12
+ * (RequestFailedFromServer) have no decoder here: they are returned as slices
+ * and not validated.
+ *
+ * Outputs per frame, zero-copy offsets into `wire`; an absent field gives the
+ * frame's own offset and length 0; a frame that is not OK has kind 0, timestamp
+ * 0 and every length 0 (offsets: the frame's own).  kind: 0 = PAYLOAD_NOT_SET,
+ * otherwise the field number - 100 (1..12); a present, empty payload has length
+ * 0 and its kind.
+ * ------------------------------------------------------------------------ */
+enum mochi_env_status { MOCHI_ENV_OK = 0, MOCHI_ENV_MALFORMED = 1, MOCHI_ENV_FALLBACK = 2 };
+#define MOCHI_ENV_KINDS 13 /* payload cases: 0 = not set, k = field number - 100 */
+typedef struct mochi_envelope_frames {
+  uint32_t n_frames, _pad0;
+  const uint8_t*  wire;    uint64_t wire_len;
+  const uint64_t* frame_off;   /* [n] */
+  const uint32_t* frame_len;   /* [n] */
+} mochi_envelope_frames;
+typedef struct mochi_envelope_decoded {
+  uint8_t*  status;            /* [n] enum mochi_env_status */
+  uint8_t*  kind;              /* [n] 0..12 */
+  uint64_t* body_off;          /* [n] the payload's value */
+  uint32_t* body_len;
+  int64_t*  msg_timestamp;     /* [n] */
+  uint64_t* server_id_off;     /* [n] */
+  uint32_t* server_id_len;
+  uint64_t* msg_id_off;        /* [n] */
+  uint32_t* msg_id_len;
+  uint64_t* reply_to_off;      /* [n] */
+  uint32_t* reply_to_len;
+} mochi_envelope_decoded;
+/* Host form.  MOCHI_EINVAL for a NULL array, more than 2^24 frames or a frame
+ * slice outside wire.  With n_frames == 0 no pointer is needed. */
+int mochi_envelope_decode(const mochi_envelope_frames* frames, mochi_envelope_decoded* out);
+/* Device form: every array in DEVICE memory, the structs on the host; one
+ * kernel (k_env_decode, lane = frame) on `stream`, no host wait, no scratch. */
+int mochi_envelope_decode_device(mochi_ctx* ctx, const mochi_envelope_frames* frames, mochi_envelope_decoded* out,
+                                 void* stream);
+
+/* ROUTE, the server's side.  From the decode's status / kind / body_off /
+ * body_len: kind_off[14], a CSR over the kinds 0..12 (kind_off[13] = the number
+ * routed); order[], the indices of the OK frames kind-major, in frame order
+ * inside a kind; body_off / body_len gathered in that order.  The run of kind 7
+ * is mochi_write1_requests.msg_off / msg_len as it stands (at body_off +
+ * kind_off[7], kind_off[8] - kind_off[7] long), the run of kind 10 the Write2
+ * batch's, the run of kind 5 the read requests.  Frames that are not OK (or
+ * carry a kind above 12) take no place; the entries of order / body_off /
+ * body_len from kind_off[13] on are not written. */
+typedef struct mochi_envelope_routed {
+  uint32_t* kind_off;          /* [14] */
+  uint32_t* order;             /* [n] */
+  uint64_t* body_off;          /* [n] */
+  uint32_t* body_len;          /* [n] */
+} mochi_envelope_routed;
+/* Host form.  MOCHI_EINVAL for a NULL array or more than 2^24 frames. */
+int mochi_envelope_route(uint32_t n_frames, const uint8_t* status, const uint8_t* kind, const uint64_t* body_off,
+                         const uint32_t* body_len, mochi_envelope_routed* out);
+/* Device form: every array in DEVICE memory, kind_off included; no host wait (a
+ * caller copies 14 words when it wants the counts).  The result equals the host
+ * form's array for array: ranks come from ballots and a scan over per-block
+ * histograms (k_env_hist, the scan, k_env_scatter), not from arrival at an
+ * atomic.  Scratch is the context's. */
+int mochi_envelope_route_device(mochi_ctx* ctx, uint32_t n_frames, const uint8_t* status, const uint8_t* kind,
+                                const uint64_t* body_off, const uint32_t* body_len, mochi_envelope_routed* out,
+                                void* stream);
+
+/* JOIN, the client's side.  The outstanding requests' msgIds are slices of
+ * `ids`; each OK frame's replyToMsgId is matched byte for byte against them.  An
+ * empty replyToMsgId matches nothing (nor does an empty table id); an id that
+ * occurs twice in the table resolves to the smaller request index.  Outputs:
+ * frame_req[n], the frame's request or MOCHI_W1_NONE; req_resp_off[Q+1];
+ * resp_frame[], the matched frames grouped by request, in frame order inside a
+ * request; in that order resp_off / resp_len (the body slices) and the payload
+ * case as the two reply decoders take it: resp_w1_kind (108 -> MOCHI_W1_OK, 109
+ * -> MOCHI_W1_REFUSED, 112 -> MOCHI_W1_REQUEST_FAILED, else MOCHI_W1_OTHER) and
+ * resp_rr_kind (111 -> MOCHI_RR_WRITE2_ANS, 106 -> MOCHI_RR_READ, else
+ * MOCHI_RR_OTHER); P = req_resp_off[Q], the number of matched frames.  The
+ * per-response arrays are n long; their entries from P on are not written.
+ * Frames that are MALFORMED, FALLBACK or unmatched appear in no run: a frame
+ * whose parse throws never reaches the reference's client either.  The
+ * reference's client pairs replies by connection and never reads field 8; the
+ * join by field 8 is this library's choice. */
+typedef struct mochi_envelope_requests {
+  uint32_t n_reqs, _pad0;      /* Q */
+  const uint8_t*  ids;     uint64_t ids_len;
+  const uint64_t* id_off;      /* [Q] */
+  const uint32_t* id_len;      /* [Q] */
+} mochi_envelope_requests;
+typedef struct mochi_envelope_joined {
+  uint32_t* frame_req;         /* [n] */
+  uint32_t* req_resp_off;      /* [Q+1] */
+  uint32_t* resp_frame;        /* [n], P written */
+  uint64_t* resp_off;
+  uint32_t* resp_len;
+  uint8_t*  resp_w1_kind;
+  uint8_t*  resp_rr_kind;
+} mochi_envelope_joined;
+/* Host form; *n_resps = P.  `decoded` is read (status, kind, body_off, body_len,
+ * reply_to_off, reply_to_len; the other arrays may be NULL).  MOCHI_EINVAL for a
+ * NULL array, more than 2^24 frames or requests, an id outside ids or a
+ * replyToMsgId outside wire. */
+int mochi_envelope_join(const mochi_envelope_requests* requests, const mochi_envelope_frames* frames,
+                        const mochi_envelope_decoded* decoded, mochi_envelope_joined* out, uint32_t* n_resps);
+/* Device form: every array in DEVICE memory; P goes to the device word
+ * *n_resps_dev; no host wait.  The msgId table is an open-addressing claim
+ * table in the context's scratch (k_w1q_claim's: at least 2 * Q slots, the
+ * smallest claimant wins); the grouping is a stable radix sort by request index.
+ * Array for array the host form's result. */
+int mochi_envelope_join_device(mochi_ctx* ctx, const mochi_envelope_requests* requests,
+                               const mochi_envelope_frames* frames, const mochi_envelope_decoded* decoded,
+                               mochi_envelope_joined* out, uint32_t* n_resps_dev, void* stream);
+
+/* ENCODE: wrap.  Per message a kind (0..12), a body slice of `bodies` (a body
+ * encoder's output in place; ignored for kind 0), msg_timestamp, and msgId /
+ * replyToMsgId / serverId as slices of `ids` (any pair of arrays may be NULL:
+ * every such string empty).  `ids` may be a received wire: a reply's
+ * replyToMsgId is the request's msgId slice, no copy.  Output: exactly the bytes
+ * ProtocolMessage.toByteArray() writes: fields in number order 5, 6, 7, 8, then
+ * the payload; zero and empty scalars omitted; a set payload written even when
+ * empty (DA 06 00 for kind 7); kind 0 writes no payload.  With
+ * MOCHI_ENV_LENGTH_PREFIX in `flags` ProtobufVarint32LengthFieldPrepender's
+ * varint32 goes in front of each message: msg_off / msg_len still name the
+ * message, the prefix lies in the bytes just before it. */
+#define MOCHI_ENV_LENGTH_PREFIX 0x1
+typedef struct mochi_envelope_source {
+  uint32_t n_msgs, flags;      /* M; MOCHI_ENV_* */
+  const uint8_t*  bodies;  uint64_t bodies_len;
+  const uint8_t*  ids;     uint64_t ids_len;
+  const uint8_t*  kind;            /* [M] */
+  const uint64_t* body_off;        /* [M] into bodies */
+  const uint32_t* body_len;
+  const int64_t*  msg_timestamp;   /* [M] */
+  const uint64_t* msg_id_off;      /* [M] into ids; NULL with msg_id_len = every msgId empty */
+  const uint32_t* msg_id_len;
+  const uint64_t* reply_to_off;    /* [M] into ids */
+  const uint32_t* reply_to_len;
+  const uint64_t* server_id_off;   /* [M] into ids */
+  const uint32_t* server_id_len;
+} mochi_envelope_source;
+/* A safe wire_cap from counts and blob lengths alone. */
+uint64_t mochi_envelope_encode_bound(uint32_t n_msgs, uint64_t bodies_len, uint64_t ids_len);
+/* Host form.  Outputs, capacity rule and argument order as
+ * mochi_result_reply_encode: messages packed back to back in order with 64-bit
+ * offsets, status[m] enum mochi_enc_status (MOCHI_ENC_TOO_LONG gives length 0),
+ * *wire_len the total; MOCHI_EINVAL with *wire_len set and no byte written when
+ * wire_cap is smaller.  MOCHI_EINVAL also for a kind above 12, an id that is
+ * not UTF-8, a slice outside its blob, unknown flags or a NULL required array.
+ * With n_msgs == 0 no pointer but wire_len is needed. */
+int mochi_envelope_encode(const mochi_envelope_source* src, uint8_t* wire_out, uint64_t wire_cap, uint64_t* msg_off,
+                          uint32_t* msg_len, uint8_t* status, uint64_t* wire_len);
+/* Device form: every array in DEVICE memory, the two capacity modes of
+ * mochi_result_reply_encode_device.  The caller's arrays are trusted, their
+ * values are not: a kind above 12 is MOCHI_ENC_BAD_KIND and an id that is not
+ * UTF-8 MOCHI_ENC_BAD_ID for that message, which is emitted with length 0 (with
+ * the prefix flag: the one byte 00), and the call succeeds.  k_env_size, the
+ * offset scan, k_env_hdr, and k_env_copy, which copies the bodies with the
+ * encoders' shared chunk copy (16 lanes per short body, one wave per long one). */
+int mochi_envelope_encode_device(mochi_ctx* ctx, const mochi_envelope_source* src, uint8_t* wire_out,
+                                 uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len, uint8_t* status,
+                                 uint64_t* wire_len, uint64_t* wire_len_dev, void* stream);
+/* Per-kernel device time (ms) of the last device call of kind `which` made while
+ * profiling was on.  Waits for that call.
+ *   MOCHI_ENV_PROF_DECODE  [0] k_env_decode
+ *   MOCHI_ENV_PROF_ROUTE   [0] k_env_hist, [1] the scan, [2] k_env_scatter
+ *   MOCHI_ENV_PROF_JOIN    [0] table clear + k_env_claim, [1] k_env_lookup, [2] the sort, [3] k_env_group
+ *   MOCHI_ENV_PROF_ENCODE  [0] k_env_size, [1] the offset scan, [2] k_env_hdr, [3] k_env_copy
+ * n_kernels <= 4; entries past the call's stages are 0. */
+#define MOCHI_ENV_PROF_DECODE 0
+#define MOCHI_ENV_PROF_ROUTE 1
+#define MOCHI_ENV_PROF_JOIN 2
+#define MOCHI_ENV_PROF_ENCODE 3
+int mochi_ctx_read_envelope_profile(mochi_ctx* ctx, int which, float* kernel_ms, uint32_t n_kernels);
 
 /* ------------------------------------------------------------------------
  * Micro-batcher: the blocking per-request call the Java handler keeps

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "envelope.h"
 #include "mont.h"
 #include "result_decode.h"
 #include "result_encode.h"
@@ -2002,6 +2003,284 @@ int mochi_write2_answer_plan_device(const mochi_write2_batch* b, const mochi_wri
   const mochi::rae::PlanView v{*b, *s, *o};
   HIP_TRY(mochi::launch_w2a_plan(v, (hipStream_t)stream));
   return MOCHI_OK;
+}
+
+}  // extern "C"
+
+// ---- the ProtocolMessage envelope (envelope.hip / envelope_host.cpp) ----
+namespace {
+
+int check_env_frames(const mochi_envelope_frames* f) {
+  if (!f) return fail(MOCHI_EINVAL, "null argument");
+  if (f->n_frames > mochi::env::kMaxFrames) return fail(MOCHI_EINVAL, "more than 2^24 frames");
+  if (f->n_frames && (!f->frame_off || !f->frame_len || (!f->wire && f->wire_len)))
+    return fail(MOCHI_EINVAL, "wire / frame_off / frame_len required");
+  return MOCHI_OK;
+}
+
+int check_env_decode(const mochi_envelope_frames* f, const mochi_envelope_decoded* o) {
+  int rc = check_env_frames(f);
+  if (rc) return rc;
+  if (!o) return fail(MOCHI_EINVAL, "null argument");
+  if (f->n_frames && (!o->status || !o->kind || !o->body_off || !o->body_len || !o->msg_timestamp || !o->server_id_off ||
+                      !o->server_id_len || !o->msg_id_off || !o->msg_id_len || !o->reply_to_off || !o->reply_to_len))
+    return fail(MOCHI_EINVAL, "every output array is required");
+  return MOCHI_OK;
+}
+
+int check_env_route(uint32_t n, const uint8_t* status, const uint8_t* kind, const uint64_t* body_off,
+                    const uint32_t* body_len, const mochi_envelope_routed* o) {
+  if (!o || !o->kind_off) return fail(MOCHI_EINVAL, "kind_off required");
+  if (n > mochi::env::kMaxFrames) return fail(MOCHI_EINVAL, "more than 2^24 frames");
+  if (n && (!status || !kind || !body_off || !body_len)) return fail(MOCHI_EINVAL, "status / kind / body_off / body_len required");
+  if (n && (!o->order || !o->body_off || !o->body_len)) return fail(MOCHI_EINVAL, "every output array is required");
+  return MOCHI_OK;
+}
+
+int check_env_join(const mochi_envelope_requests* r, const mochi_envelope_frames* f, const mochi_envelope_decoded* d,
+                   const mochi_envelope_joined* o) {
+  int rc = check_env_frames(f);
+  if (rc) return rc;
+  if (!r || !d || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (r->n_reqs > mochi::env::kMaxFrames) return fail(MOCHI_EINVAL, "more than 2^24 requests");
+  if (r->n_reqs && (!r->id_off || !r->id_len || (!r->ids && r->ids_len))) return fail(MOCHI_EINVAL, "ids / id_off / id_len required");
+  if (!o->req_resp_off) return fail(MOCHI_EINVAL, "req_resp_off required");
+  if (f->n_frames && (!d->status || !d->kind || !d->body_off || !d->body_len || !d->reply_to_off || !d->reply_to_len))
+    return fail(MOCHI_EINVAL, "status / kind / body_off / body_len / reply_to_off / reply_to_len required");
+  if (f->n_frames && (!o->frame_req || !o->resp_frame || !o->resp_off || !o->resp_len || !o->resp_w1_kind || !o->resp_rr_kind))
+    return fail(MOCHI_EINVAL, "every output array is required");
+  return MOCHI_OK;
+}
+
+int check_env_source(const mochi_envelope_source* s, const uint8_t* wire, uint64_t wire_cap, const uint64_t* msg_off,
+                     const uint32_t* msg_len, const uint8_t* status) {
+  if (!s) return fail(MOCHI_EINVAL, "null argument");
+  if (s->n_msgs == 0xFFFFFFFFu) return fail(MOCHI_EINVAL, "batch too large");
+  if (s->flags & ~(uint32_t)MOCHI_ENV_LENGTH_PREFIX) return fail(MOCHI_EINVAL, "unknown flags");
+  if (!s->n_msgs) return MOCHI_OK;
+  if (!s->kind || !s->body_off || !s->body_len || !s->msg_timestamp || !msg_off || !msg_len || !status)
+    return fail(MOCHI_EINVAL, "kind / body_off / body_len / msg_timestamp / msg_off / msg_len / status required");
+  if (!s->msg_id_off != !s->msg_id_len) return fail(MOCHI_EINVAL, "msg_id_off and msg_id_len go together");
+  if (!s->reply_to_off != !s->reply_to_len) return fail(MOCHI_EINVAL, "reply_to_off and reply_to_len go together");
+  if (!s->server_id_off != !s->server_id_len) return fail(MOCHI_EINVAL, "server_id_off and server_id_len go together");
+  if ((s->msg_id_off || s->reply_to_off || s->server_id_off) && s->ids_len && !s->ids) return fail(MOCHI_EINVAL, "ids required");
+  if (s->bodies_len && !s->bodies) return fail(MOCHI_EINVAL, "bodies required");
+  if (wire_cap && !wire) return fail(MOCHI_EINVAL, "wire_out required");
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mochi_envelope_decode(const mochi_envelope_frames* f, mochi_envelope_decoded* o) {
+  int rc = check_env_decode(f, o);
+  if (rc || !f->n_frames) return rc;
+  const char* err = "";
+  rc = mochi_host::envelope_decode(f, o, &err);
+  return rc ? fail(rc, "mochi_envelope_decode: %s", err) : MOCHI_OK;
+}
+
+int mochi_envelope_decode_device(mochi_ctx* c, const mochi_envelope_frames* f, mochi_envelope_decoded* o, void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  int rc = check_env_decode(f, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  EncState& x = c->env_dec;
+  x.ev_valid = false;
+  if (!f->n_frames) return MOCHI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  mochi::EnvDecArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.in = *f;
+  a.v.out = *o;
+  if ((rc = x.events(c->profiling, mochi::kEnvDecEvents, &a.ev))) return rc;
+  // no scratch, but the call still orders itself behind the context's last call on another stream
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_env_decode(a, st));
+  x.ev_valid = a.ev != nullptr;
+  HIP_TRY(c->order.release(st));
+  return MOCHI_OK;
+}
+
+int mochi_envelope_route(uint32_t n, const uint8_t* status, const uint8_t* kind, const uint64_t* body_off,
+                         const uint32_t* body_len, mochi_envelope_routed* o) {
+  int rc = check_env_route(n, status, kind, body_off, body_len, o);
+  if (rc) return rc;
+  const mochi::env::RouteView v{n, status, kind, body_off, body_len, *o};
+  const char* err = "";
+  rc = mochi_host::envelope_route(&v, &err);
+  return rc ? fail(rc, "mochi_envelope_route: %s", err) : MOCHI_OK;
+}
+
+int mochi_envelope_route_device(mochi_ctx* c, uint32_t n, const uint8_t* status, const uint8_t* kind,
+                                const uint64_t* body_off, const uint32_t* body_len, mochi_envelope_routed* o, void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  int rc = check_env_route(n, status, kind, body_off, body_len, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  EncState& x = c->env_route;
+  x.ev_valid = false;
+  hipStream_t st = (hipStream_t)stream;
+  if (!n) {
+    HIP_TRY(hipMemsetAsync(o->kind_off, 0, 4 * (MOCHI_ENV_KINDS + 1), st));
+    return MOCHI_OK;
+  }
+  mochi::EnvRouteArgs a;
+  memset(&a, 0, sizeof a);
+  a.v = mochi::env::RouteView{n, status, kind, body_off, body_len, *o};
+  a.blocks = (n + 255) / 256;
+  if ((rc = x.begin(a, mochi::env_route_layout, mochi::env_route_scan_n(a.blocks), 0, c->profiling, mochi::kEnvRouteEvents)))
+    return rc;
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_env_route(a, st));
+  x.ev_valid = a.ev != nullptr;
+  HIP_TRY(c->order.release(st));
+  return MOCHI_OK;
+}
+
+int mochi_envelope_join(const mochi_envelope_requests* r, const mochi_envelope_frames* f, const mochi_envelope_decoded* d,
+                        mochi_envelope_joined* o, uint32_t* n_resps) {
+  if (!n_resps) return fail(MOCHI_EINVAL, "n_resps required");
+  *n_resps = 0;
+  int rc = check_env_join(r, f, d, o);
+  if (rc) return rc;
+  const mochi::env::JoinView v{*r, *f, *d, *o};
+  const char* err = "";
+  rc = mochi_host::envelope_join(&v, n_resps, &err);
+  return rc ? fail(rc, "mochi_envelope_join: %s", err) : MOCHI_OK;
+}
+
+int mochi_envelope_join_device(mochi_ctx* c, const mochi_envelope_requests* r, const mochi_envelope_frames* f,
+                               const mochi_envelope_decoded* d, mochi_envelope_joined* o, uint32_t* n_resps_dev,
+                               void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  if (!n_resps_dev) return fail(MOCHI_EINVAL, "n_resps_dev required");
+  int rc = check_env_join(r, f, d, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  EncState& x = c->env_join;
+  x.ev_valid = false;
+  hipStream_t st = (hipStream_t)stream;
+  mochi::EnvJoinArgs a;
+  memset(&a, 0, sizeof a);
+  a.v = mochi::env::JoinView{*r, *f, *d, *o};
+  a.slots = mochi::env::join_slots(r->n_reqs);
+  a.key_bits = mochi::env::join_key_bits(r->n_reqs);
+  a.n_resps = n_resps_dev;
+  if ((rc = x.begin(a, mochi::env_join_layout, 0, 0, c->profiling, mochi::kEnvJoinEvents))) return rc;
+  if (f->n_frames) {
+    size_t sort_bytes = 0;
+    HIP_TRY(mochi::env_sort_temp_bytes(f->n_frames, a.key_bits, &sort_bytes));
+    if ((rc = x.scan.ensure(sort_bytes))) return rc;
+    a.scan_temp = x.scan.p;
+    a.scan_temp_bytes = x.scan.cap;
+  }
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_env_join(a, st));
+  x.ev_valid = a.ev != nullptr;
+  HIP_TRY(c->order.release(st));
+  return MOCHI_OK;
+}
+
+uint64_t mochi_envelope_encode_bound(uint32_t n_msgs, uint64_t bodies_len, uint64_t ids_len) {
+  // every body at bodies_len and every id at ids_len, five-byte length varints, a ten-byte
+  // timestamp and a five-byte prefix throughout
+  unsigned __int128 t = (unsigned __int128)n_msgs * ((unsigned __int128)bodies_len + 3 * (unsigned __int128)ids_len + 41);
+  const unsigned __int128 cap = (unsigned __int128)n_msgs * (mochi::kEncMaxMsg + 5);  // longer messages are emitted empty
+  if (t > cap) t = cap;
+  return (uint64_t)t;
+}
+
+int mochi_envelope_encode(const mochi_envelope_source* s, uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off,
+                          uint32_t* msg_len, uint8_t* status, uint64_t* wire_len) {
+  if (!wire_len) return fail(MOCHI_EINVAL, "wire_len required");
+  *wire_len = 0;
+  int rc = check_env_source(s, wire, wire_cap, msg_off, msg_len, status);
+  if (rc || !s->n_msgs) return rc;
+  const char* err = "";
+  rc = mochi_host::envelope_encode(s, wire, wire_cap, msg_off, msg_len, status, wire_len, &err);
+  return rc ? fail(rc, "mochi_envelope_encode: %s", err) : MOCHI_OK;
+}
+
+int mochi_envelope_encode_device(mochi_ctx* c, const mochi_envelope_source* s, uint8_t* wire, uint64_t wire_cap,
+                                 uint64_t* msg_off, uint32_t* msg_len, uint8_t* status, uint64_t* wire_len,
+                                 uint64_t* wire_len_dev, void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  if (!wire_len && !wire_len_dev) return fail(MOCHI_EINVAL, "wire_len or wire_len_dev required");
+  int rc = check_env_source(s, wire, wire_cap, msg_off, msg_len, status);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t M = s->n_msgs;
+  EncState& x = c->env_enc;
+  if (wire_len) *wire_len = 0;
+  x.ev_valid = false;
+  if (M == 0) {
+    if (!wire_len) HIP_TRY(hipMemsetAsync(wire_len_dev, 0, 8, st));
+    return MOCHI_OK;
+  }
+  mochi::EnvEncArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = *s;
+  a.wire = wire;
+  a.wire_cap = wire_cap;
+  a.msg_off = msg_off;
+  a.msg_len = msg_len;
+  a.status = status;
+  if ((rc = x.begin(a, mochi::env_enc_layout, mochi::w2_small(M) ? 0 : M + 1, 8, c->profiling, mochi::kEnvEncEvents))) return rc;
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_env_size(a, st));
+  bool fits = true;
+  uint64_t need = 0;
+  if (wire_len) {
+    if ((rc = x.fetch_totals(a.off64 + M, 8, c->ev_tot, st))) return rc;
+    *wire_len = need = *(const uint64_t*)x.tot.p;
+    fits = need <= wire_cap;
+  } else {
+    HIP_TRY(hipMemcpyAsync(wire_len_dev, a.off64 + M, 8, hipMemcpyDeviceToDevice, st));
+  }
+  // k_env_hdr runs either way: it writes msg_off, and reads the total before it writes a byte of wire
+  HIP_TRY(mochi::launch_env_emit(a, fits, st));
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(c->order.release(st));
+  return fits ? MOCHI_OK : capacity_error("wire_cap", wire_cap, "encoded size", need);
+}
+
+int mochi_ctx_read_envelope_profile(mochi_ctx* c, int which, float* kernel_ms, uint32_t n_kernels) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  static const int kDec[mochi::kEnvDecStages][2] = {{0, 1}};
+  static const int kRoute[mochi::kEnvRouteStages][2] = {{0, 1}, {1, 2}, {2, 3}};
+  static const int kJoin[mochi::kEnvJoinStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+  static const int kEnc[mochi::kEnvEncStages][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+  switch (which) {
+    case MOCHI_ENV_PROF_DECODE:
+      return c->env_dec.read_profile(kDec, mochi::kEnvDecStages, kernel_ms, n_kernels,
+                                     "no envelope decode call was made while profiling was on");
+    case MOCHI_ENV_PROF_ROUTE:
+      return c->env_route.read_profile(kRoute, mochi::kEnvRouteStages, kernel_ms, n_kernels,
+                                       "no envelope route call was made while profiling was on");
+    case MOCHI_ENV_PROF_JOIN:
+      return c->env_join.read_profile(kJoin, mochi::kEnvJoinStages, kernel_ms, n_kernels,
+                                      "no envelope join call was made while profiling was on");
+    case MOCHI_ENV_PROF_ENCODE:
+      return c->env_enc.read_profile(kEnc, mochi::kEnvEncStages, kernel_ms, n_kernels,
+                                     "no envelope encode call was made while profiling was on");
+  }
+  return fail(MOCHI_EINVAL, "which is no MOCHI_ENV_PROF_*");
 }
 
 }  // extern "C"

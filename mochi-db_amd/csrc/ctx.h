@@ -204,6 +204,9 @@ struct mochi_ctx {
   mochi::DevBuf w1d_sig;  // ... and its signature sources, sized once the grant total is known
   mochi::EncState rr;   // result reply decoder (result_decode.hip); it waits for no total
   mochi::EncState rae;  // answer encoder (result_encode.hip); its total is the wire size
+  // envelope codec (envelope.hip), one state per call so that each keeps its last profile:
+  // decode (events alone), route, join (its `scan` is the radix sort's temp), encode
+  mochi::EncState env_dec, env_route, env_join, env_enc;
   // the last host-path call's certificate accept bitmap on the device (a slice
   // of dev_out, valid until the next call on this context; nullptr when the
   // device copy is not the final verdict, e.g. after host fallback decisions):

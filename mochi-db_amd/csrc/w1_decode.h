@@ -204,6 +204,22 @@ W1D_HD bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n) {
     if (a[i] != b[i]) return false;
   return true;
 }
+// FNV-1a over the bytes, then a finalizer (murmur3's) so that strings that differ in
+// their last byte alone spread over a table: the slot hash of the claim tables
+// (w1_request.hip's key table, envelope.hip's msgId table).  It decides no output.
+W1D_HD uint32_t bytes_hash(const uint8_t* k, uint32_t n) {
+  uint32_t h = 0x811C9DC5u;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (uint32_t i = 0; i < n; i++) h = (h ^ k[i]) * 0x01000193u;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
 W1D_HD bool key_eq(const uint8_t* p, uint32_t a, uint32_t al, uint32_t b, uint32_t bl) {
   return al == bl && (a == b || bytes_eq(p + a, p + b, al));
 }

@@ -112,18 +112,10 @@ __global__ __launch_bounds__(256) void k_w1q_emit(W1ReqArgs a) {
   emit_op(a.v, lo, l.x, l.y, o - (uint32_t)a.off64[lo], o);
 }
 
-// FNV-1a over the key bytes, then a finalizer (murmur3's) so that keys that differ in
-// their last byte alone spread over the table
+// the slot a key's probe starts at (w1_decode.h bytes_hash: keys that differ in their
+// last byte alone spread over the table)
 __device__ __forceinline__ uint32_t key_slot(const uint8_t* __restrict__ k, uint32_t n, uint32_t mask) {
-  uint32_t h = 0x811C9DC5u;
-#pragma unroll 1
-  for (uint32_t i = 0; i < n; i++) h = (h ^ k[i]) * 0x01000193u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h & mask;
+  return w1d::bytes_hash(k, n) & mask;
 }
 
 __global__ __launch_bounds__(256) void k_w1q_claim(W1ReqArgs a) {

@@ -229,6 +229,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_ctx_read_result_encode_profile.argtypes = [vp, vp, u32]
     lib.mochi_write2_answer_plan.argtypes = [vp, vp, vp]
     lib.mochi_write2_answer_plan_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_envelope_decode.argtypes = [vp, vp]
+    lib.mochi_envelope_decode_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_envelope_route.argtypes = [u32, vp, vp, vp, vp, vp]
+    lib.mochi_envelope_route_device.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.mochi_envelope_join.argtypes = [vp, vp, vp, vp, vp]
+    lib.mochi_envelope_join_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.mochi_envelope_encode_bound.restype = u64
+    lib.mochi_envelope_encode_bound.argtypes = [u32, u64, u64]
+    lib.mochi_envelope_encode.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+    lib.mochi_envelope_encode_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.mochi_ctx_read_envelope_profile.argtypes = [vp, ctypes.c_int, vp, u32]
     lib.mochi_batcher_create.restype = vp
     lib.mochi_batcher_create.argtypes = [vp, vp, u32, u32, ctypes.c_int]
     lib.mochi_batcher_create_multi.restype = vp
@@ -643,6 +654,57 @@ class Verifier:
         if self.lib.mochi_ctx_read_result_encode_profile(self.ctx, _ptr(ms), ms.size) != OK:
             raise MochiError(f"mochi_ctx_read_result_encode_profile: {_err(self.lib)}")
         return dict(zip(RESULT_ENCODE_STAGES, (float(x) for x in ms)))
+
+    def envelope_decode_device(self, dframes: "DeviceEnvelopeFrames", out: "DeviceEnvelopeDecoded",
+                               stream: int = 0) -> None:
+        """mochi_envelope_decode_device: device-resident frames -> the arrays of `out`; no wait."""
+        f, o = dframes.to_c(), out.to_c()
+        rc = self.lib.mochi_envelope_decode_device(self.ctx, ctypes.addressof(f), ctypes.addressof(o), stream or None)
+        if rc != OK:
+            raise MochiError(f"mochi_envelope_decode_device rc={rc}: {_err(self.lib)}")
+
+    def envelope_route_device(self, dec: "DeviceEnvelopeDecoded", out: "DeviceEnvelopeRouted", stream: int = 0) -> None:
+        """mochi_envelope_route_device over the decode's outputs; kind_off stays on the device; no wait."""
+        o = out.to_c()
+        rc = self.lib.mochi_envelope_route_device(self.ctx, dec.n, dec.status.data_ptr(), dec.kind.data_ptr(),
+                                                  dec.body_off.data_ptr(), dec.body_len.data_ptr(), ctypes.addressof(o),
+                                                  stream or None)
+        if rc != OK:
+            raise MochiError(f"mochi_envelope_route_device rc={rc}: {_err(self.lib)}")
+
+    def envelope_join_device(self, dreqs: "DeviceEnvelopeRequests", dframes: "DeviceEnvelopeFrames",
+                             dec: "DeviceEnvelopeDecoded", out: "DeviceEnvelopeJoined", stream: int = 0) -> None:
+        """mochi_envelope_join_device: the replies of `dframes` grouped by request into `out`
+        (out.n_resps: the device word P goes to); no wait."""
+        r, f, d, o = dreqs.to_c(), dframes.to_c(), dec.to_c(), out.to_c()
+        rc = self.lib.mochi_envelope_join_device(self.ctx, ctypes.addressof(r), ctypes.addressof(f), ctypes.addressof(d),
+                                                 ctypes.addressof(o), out.n_resps.data_ptr(), stream or None)
+        if rc != OK:
+            raise MochiError(f"mochi_envelope_join_device rc={rc}: {_err(self.lib)}")
+
+    def envelope_encode_device(self, dsrc: "DeviceEnvelopeSource", wire, msg_off, msg_len, status, stream: int = 0,
+                               wire_len_dev=None, check: bool = True):
+        """mochi_envelope_encode_device; arguments and result as result_reply_encode_device."""
+        s = dsrc.to_c()
+        cap = 0 if wire is None else int(wire.numel())
+        need = ctypes.c_uint64(0)
+        rc = self.lib.mochi_envelope_encode_device(
+            self.ctx, ctypes.addressof(s), wire.data_ptr() if cap else None, cap, msg_off.data_ptr(), msg_len.data_ptr(),
+            status.data_ptr(), ctypes.addressof(need) if wire_len_dev is None else None,
+            None if wire_len_dev is None else wire_len_dev.data_ptr(), stream or None)
+        short = wire_len_dev is None and rc == EINVAL and int(need.value) > cap
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_envelope_encode_device rc={rc}: {_err(self.lib)}")
+        return rc, (int(need.value) if wire_len_dev is None else None)
+
+    def read_envelope_profile(self, which: str) -> dict:
+        """Per-kernel ms of the last envelope_<which>_device call made with set_profiling(True);
+        which: "decode", "route", "join" or "encode"."""
+        names = ENVELOPE_STAGES[which]
+        ms = np.zeros(len(names), np.float32)
+        if self.lib.mochi_ctx_read_envelope_profile(self.ctx, list(ENVELOPE_STAGES).index(which), _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_envelope_profile: {_err(self.lib)}")
+        return dict(zip(names, (float(x) for x in ms)))
 
     def decode_write2(self, wb) -> dict:
         """The device decoder's SoA view of the messages (inspection / tests)."""
@@ -2901,6 +2963,370 @@ def write2_answer_plan_device(dwb: "DeviceWireBatch", verdicts: "DeviceVerdicts"
     rc = lib.mochi_write2_answer_plan_device(ctypes.addressof(b), ctypes.addressof(s), ctypes.addressof(o), stream or None)
     if rc != OK:
         raise MochiError(f"mochi_write2_answer_plan_device rc={rc}: {_err(lib)}")
+
+
+# ---------------------------------------------------------------------------
+# The ProtocolMessage envelope: frames -> status / payload case / body slice / scalars
+# (decode), the server's partition by case (route), the client's match of replies to
+# requests (join), and bodies -> frames (encode)
+# ---------------------------------------------------------------------------
+ENV_OK, ENV_MALFORMED, ENV_FALLBACK = range(3)
+ENV_KINDS = 13
+ENV_LENGTH_PREFIX = 0x1
+ENC_BAD_KIND, ENC_BAD_ID = 5, 6
+ENVELOPE_STAGES = dict(decode=("k_env_decode",), route=("k_env_hist", "scan", "k_env_scatter"),
+                       join=("k_env_claim", "k_env_lookup", "sort", "k_env_group"),
+                       encode=("k_env_size", "scan", "k_env_hdr", "k_env_copy"))
+
+_ENV_DEC = dict(status=np.uint8, kind=np.uint8, body_off=np.uint64, body_len=np.uint32, msg_timestamp=np.int64,
+                server_id_off=np.uint64, server_id_len=np.uint32, msg_id_off=np.uint64, msg_id_len=np.uint32,
+                reply_to_off=np.uint64, reply_to_len=np.uint32)
+# the routed / joined outputs: "n" per frame, "K" the 14 kind offsets, "Q1" per request + 1
+_ENV_ROUTED = dict(kind_off=(np.uint32, "K"), order=(np.uint32, "n"), body_off=(np.uint64, "n"), body_len=(np.uint32, "n"))
+_ENV_JOINED = dict(frame_req=(np.uint32, "n"), req_resp_off=(np.uint32, "Q1"), resp_frame=(np.uint32, "n"),
+                   resp_off=(np.uint64, "n"), resp_len=(np.uint32, "n"), resp_w1_kind=(np.uint8, "n"),
+                   resp_rr_kind=(np.uint8, "n"))
+# the per-message arrays of mochi_envelope_source; "?" may be None
+_ENV_SRC = dict(kind=(np.uint8, ""), body_off=(np.uint64, ""), body_len=(np.uint32, ""), msg_timestamp=(np.int64, ""),
+                msg_id_off=(np.uint64, "?"), msg_id_len=(np.uint32, "?"), reply_to_off=(np.uint64, "?"),
+                reply_to_len=(np.uint32, "?"), server_id_off=(np.uint64, "?"), server_id_len=(np.uint32, "?"))
+
+
+class EnvelopeFrames_C(ctypes.Structure):
+    _fields_ = [("n_frames", ctypes.c_uint32), ("_pad0", ctypes.c_uint32), ("wire", ctypes.c_void_p),
+                ("wire_len", ctypes.c_uint64), ("frame_off", ctypes.c_void_p), ("frame_len", ctypes.c_void_p)]
+
+
+class EnvelopeDecoded_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _ENV_DEC]
+
+
+class EnvelopeRouted_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _ENV_ROUTED]
+
+
+class EnvelopeRequests_C(ctypes.Structure):
+    _fields_ = [("n_reqs", ctypes.c_uint32), ("_pad0", ctypes.c_uint32), ("ids", ctypes.c_void_p),
+                ("ids_len", ctypes.c_uint64), ("id_off", ctypes.c_void_p), ("id_len", ctypes.c_void_p)]
+
+
+class EnvelopeJoined_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _ENV_JOINED]
+
+
+class EnvelopeSource_C(ctypes.Structure):
+    _fields_ = [("n_msgs", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("bodies", ctypes.c_void_p),
+                ("bodies_len", ctypes.c_uint64), ("ids", ctypes.c_void_p), ("ids_len", ctypes.c_uint64)] + \
+        [(k, ctypes.c_void_p) for k in _ENV_SRC]
+
+
+def _some(a, dt) -> np.ndarray:
+    """C-contiguous in the ABI dtype; an empty array still gets a valid address."""
+    a = np.ascontiguousarray(a, dt).reshape(-1)
+    return a if a.size else np.zeros(1, dt)
+
+
+def _filled(n: int, dt, fill: int) -> np.ndarray:
+    return np.full(max(int(n), 1) * np.dtype(dt).itemsize, fill & 0xFF, np.uint8).view(dt)
+
+
+@dataclass
+class EnvelopeFrames:
+    """Received frames (mochi_envelope_frames, host arrays): frame f is wire[frame_off[f], +frame_len[f])."""
+
+    wire: np.ndarray  # uint8
+    frame_off: np.ndarray  # uint64 [n]
+    frame_len: np.ndarray  # uint32 [n]
+
+    @classmethod
+    def pack(cls, frames: Sequence[bytes], pad: int = 0) -> "EnvelopeFrames":
+        """Frames back to back, frame i behind (i * pad) % 4 filler bytes (misaligned slices)."""
+        parts, off, pos = [], [], 0
+        for i, f in enumerate(frames):
+            p = (i * pad) % 4
+            parts.append(b"\xEE" * p)
+            off.append(pos + p)
+            parts.append(bytes(f))
+            pos += p + len(f)
+        return cls(np.frombuffer(b"".join(parts), np.uint8).copy(), np.array(off, np.uint64),
+                   np.array([len(f) for f in frames], np.uint32))
+
+    @property
+    def n_frames(self) -> int:
+        return int(np.asarray(self.frame_off).shape[0])
+
+    def to_c(self):
+        arrs = dict(wire=_some(self.wire, np.uint8), frame_off=_some(self.frame_off, np.uint64),
+                    frame_len=_some(self.frame_len, np.uint32))
+        c = EnvelopeFrames_C()
+        c.n_frames, c.wire_len = self.n_frames, int(np.asarray(self.wire).size)
+        for k, a in arrs.items():
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def _env_out(cls_c, spec: dict, sizes: dict, fill: int):
+    arr = {k: _filled(sizes[w], dt, fill) for k, (dt, w) in spec.items()}
+    o = cls_c()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a))
+    return o, arr, {k: a[:sizes[spec[k][1]]] for k, a in arr.items()}
+
+
+def envelope_decode(frames: "EnvelopeFrames", fill: int = 0) -> dict:
+    """mochi_envelope_decode (host form) into buffers prefilled with `fill`: the arrays of
+    mochi_envelope_decoded by name."""
+    lib = load_library()
+    f, keep = frames.to_c()
+    o, arr, out = _env_out(EnvelopeDecoded_C, {k: (dt, "n") for k, dt in _ENV_DEC.items()}, dict(n=frames.n_frames), fill)
+    rc = lib.mochi_envelope_decode(ctypes.addressof(f), ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_envelope_decode rc={rc}: {_err(lib)}")
+    return out
+
+
+def envelope_route(decoded: dict, fill: int = 0) -> dict:
+    """mochi_envelope_route (host form) over a decode's outputs: the arrays of
+    mochi_envelope_routed by name, order / body_off / body_len whole (n long)."""
+    lib = load_library()
+    n = int(np.asarray(decoded["status"]).shape[0])
+    ins = [_some(decoded[k], _ENV_DEC[k]) for k in ("status", "kind", "body_off", "body_len")]
+    o, arr, out = _env_out(EnvelopeRouted_C, _ENV_ROUTED, dict(n=n, K=ENV_KINDS + 1), fill)
+    rc = lib.mochi_envelope_route(n, *[_ptr(a) for a in ins], ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_envelope_route rc={rc}: {_err(lib)}")
+    return out
+
+
+def _env_requests_c(ids: Sequence[bytes]):
+    blob = _some(np.frombuffer(b"".join(ids), np.uint8), np.uint8)
+    ln = np.array([len(i) for i in ids], np.uint32)
+    off = np.concatenate([[0], np.cumsum(ln, dtype=np.uint64)[:-1]]).astype(np.uint64) if len(ids) else np.zeros(0, np.uint64)
+    arrs = dict(ids=blob, id_off=_some(off, np.uint64), id_len=_some(ln, np.uint32))
+    c = EnvelopeRequests_C()
+    c.n_reqs, c.ids_len = len(ids), sum(len(i) for i in ids)
+    for k, a in arrs.items():
+        setattr(c, k, _ptr(a))
+    return c, arrs
+
+
+def envelope_join(request_ids: Sequence[bytes], frames: "EnvelopeFrames", decoded: dict, fill: int = 0):
+    """mochi_envelope_join (host form): the outstanding requests' msgIds, the frames and
+    their decode -> (the arrays of mochi_envelope_joined by name, whole; P)."""
+    lib = load_library()
+    r, keep_r = _env_requests_c(request_ids)
+    f, keep_f = frames.to_c()
+    d = EnvelopeDecoded_C()
+    ins = {k: _some(decoded[k], dt) for k, dt in _ENV_DEC.items()}
+    for k, a in ins.items():
+        setattr(d, k, _ptr(a))
+    o, arr, out = _env_out(EnvelopeJoined_C, _ENV_JOINED, dict(n=frames.n_frames, Q1=len(request_ids) + 1), fill)
+    P = ctypes.c_uint32(0)
+    rc = lib.mochi_envelope_join(ctypes.addressof(r), ctypes.addressof(f), ctypes.addressof(d), ctypes.addressof(o),
+                                 ctypes.addressof(P))
+    if rc != OK:
+        raise MochiError(f"mochi_envelope_join rc={rc}: {_err(lib)}")
+    return out, int(P.value)
+
+
+@dataclass
+class EnvelopeSource:
+    """What to wrap (mochi_envelope_source, host arrays).  Any id pair may be None."""
+
+    bodies: np.ndarray  # uint8
+    ids: np.ndarray  # uint8
+    kind: np.ndarray  # uint8 [M]
+    body_off: np.ndarray  # uint64 [M]
+    body_len: np.ndarray  # uint32 [M]
+    msg_timestamp: np.ndarray  # int64 [M]
+    msg_id_off: Optional[np.ndarray] = None
+    msg_id_len: Optional[np.ndarray] = None
+    reply_to_off: Optional[np.ndarray] = None
+    reply_to_len: Optional[np.ndarray] = None
+    server_id_off: Optional[np.ndarray] = None
+    server_id_len: Optional[np.ndarray] = None
+    flags: int = 0
+
+    @property
+    def n_msgs(self) -> int:
+        return int(np.asarray(self.kind).shape[0])
+
+    def arrays(self) -> dict:
+        d = {k: None if getattr(self, k) is None else np.ascontiguousarray(getattr(self, k), dt).reshape(-1)
+             for k, (dt, w) in _ENV_SRC.items()}
+        d["bodies"] = np.ascontiguousarray(self.bodies, np.uint8).reshape(-1)
+        d["ids"] = np.ascontiguousarray(self.ids, np.uint8).reshape(-1)
+        return d
+
+    def to_c(self):
+        arrs = self.arrays()
+        c = EnvelopeSource_C()
+        c.n_msgs, c.flags = self.n_msgs, int(self.flags)
+        c.bodies_len, c.ids_len = int(arrs["bodies"].size), int(arrs["ids"].size)
+        for k, a in arrs.items():
+            if a is not None and a.size == 0:
+                a = arrs[k] = np.zeros(1, a.dtype)
+            setattr(c, k, _ptr(a))
+        return c, arrs
+
+
+def envelope_encode_bound(n_msgs: int, bodies_len: int, ids_len: int) -> int:
+    return int(load_library().mochi_envelope_encode_bound(n_msgs, bodies_len, ids_len))
+
+
+def envelope_encode_into(src: "EnvelopeSource", wire: Optional[np.ndarray]):
+    """mochi_envelope_encode into the caller's buffer (uint8; None = capacity 0).  Returns
+    (rc, wire_len, msg_off, msg_len, status) as result_reply_encode_into."""
+    lib = load_library()
+    s, keep = src.to_c()
+    M = src.n_msgs
+    off, ln, st = np.zeros(max(M, 1), np.uint64), np.zeros(max(M, 1), np.uint32), np.zeros(max(M, 1), np.uint8)
+    cap = 0 if wire is None else int(wire.nbytes)
+    need = ctypes.c_uint64(0)
+    rc = lib.mochi_envelope_encode(ctypes.addressof(s), _ptr(wire) if cap else None, cap, _ptr(off), _ptr(ln), _ptr(st),
+                                   ctypes.addressof(need))
+    if rc != OK and not (rc == EINVAL and int(need.value) > cap):
+        raise MochiError(f"mochi_envelope_encode rc={rc}: {_err(lib)}")
+    return rc, int(need.value), off[:M], ln[:M], st[:M]
+
+
+def envelope_encode(src: "EnvelopeSource"):
+    """Host form of the wrap: sizes first, then the frames into a buffer of exactly the size
+    needed.  Returns (wire, msg_off, msg_len, status)."""
+    rc, need, off, ln, st = envelope_encode_into(src, None)
+    wire = np.zeros(need, np.uint8)
+    if need:
+        rc, need, off, ln, st = envelope_encode_into(src, wire)
+    assert rc == OK
+    return wire, off, ln, st
+
+
+class DeviceEnvelopeFrames:
+    """An EnvelopeFrames in device memory (plumbing only): copied with torch, or built from
+    tensors that are already there (uint8 wire, int64 frame_off, int32 frame_len)."""
+
+    def __init__(self, frames: "EnvelopeFrames", device: int = 0):
+        self.n_frames, self.wire_len = frames.n_frames, int(np.asarray(frames.wire).size)
+        c, arrs = frames.to_c()
+        for k, a in arrs.items():
+            setattr(self, k, _to_dev(a, device))
+
+    @classmethod
+    def from_tensors(cls, n_frames: int, wire, frame_off, frame_len, wire_len: Optional[int] = None):
+        self = cls.__new__(cls)
+        self.n_frames, self.wire, self.frame_off, self.frame_len = int(n_frames), wire, frame_off, frame_len
+        self.wire_len = int(wire.numel()) if wire_len is None else int(wire_len)
+        return self
+
+    def to_c(self) -> EnvelopeFrames_C:
+        c = EnvelopeFrames_C()
+        c.n_frames, c.wire_len = self.n_frames, self.wire_len
+        c.wire, c.frame_off, c.frame_len = self.wire.data_ptr(), self.frame_off.data_ptr(), self.frame_len.data_ptr()
+        return c
+
+
+def _dev_i64_full(n: int, fill: int, device: int):
+    import torch
+
+    pat = int.from_bytes(bytes([fill & 0xFF]) * 8, "little", signed=True)
+    return torch.full((max(int(n), 1),), pat, dtype=torch.int64, device=torch.device("cuda", device))
+
+
+class _DevOut:
+    """Device buffers prefilled with `fill`, by a spec of (dtype, size key); uint32 as int32,
+    uint64 / int64 as int64."""
+
+    SPEC: dict = {}
+    C = None
+
+    def _alloc(self, sizes: dict, device: int, fill: int):
+        self.sizes = sizes
+        for k, (dt, w) in self.SPEC.items():
+            t = _dev_i64_full(sizes[w], fill, device) if dt == np.int64 else _dev_full(sizes[w], dt, fill, device)
+            setattr(self, k, t)
+
+    def to_c(self):
+        o = self.C()
+        for k in self.SPEC:
+            setattr(o, k, getattr(self, k).data_ptr())
+        return o
+
+    def to_host(self) -> dict:
+        """The buffers on the host, whole."""
+        return {k: getattr(self, k).cpu().numpy().view(dt)[:self.sizes[w]] for k, (dt, w) in self.SPEC.items()}
+
+
+class DeviceEnvelopeDecoded(_DevOut):
+    SPEC = {k: (dt, "n") for k, dt in _ENV_DEC.items()}
+    C = EnvelopeDecoded_C
+
+    def __init__(self, n_frames: int, device: int = 0, fill: int = 0):
+        self.n = int(n_frames)
+        self._alloc(dict(n=self.n), device, fill)
+
+
+class DeviceEnvelopeRouted(_DevOut):
+    SPEC = _ENV_ROUTED
+    C = EnvelopeRouted_C
+
+    def __init__(self, n_frames: int, device: int = 0, fill: int = 0):
+        self._alloc(dict(n=int(n_frames), K=ENV_KINDS + 1), device, fill)
+
+
+class DeviceEnvelopeJoined(_DevOut):
+    SPEC = _ENV_JOINED
+    C = EnvelopeJoined_C
+
+    def __init__(self, n_frames: int, n_reqs: int, device: int = 0, fill: int = 0):
+        self._alloc(dict(n=int(n_frames), Q1=int(n_reqs) + 1), device, fill)
+        self.n_resps = _dev_full(1, np.uint32, fill, device)
+
+
+class DeviceEnvelopeRequests:
+    """The outstanding requests' msgIds in device memory (plumbing only)."""
+
+    def __init__(self, request_ids: Sequence[bytes], device: int = 0):
+        c, arrs = _env_requests_c(request_ids)
+        self.n_reqs, self.ids_len = int(c.n_reqs), int(c.ids_len)
+        for k, a in arrs.items():
+            setattr(self, k, _to_dev(a, device))
+
+    def to_c(self) -> EnvelopeRequests_C:
+        c = EnvelopeRequests_C()
+        c.n_reqs, c.ids_len = self.n_reqs, self.ids_len
+        c.ids, c.id_off, c.id_len = self.ids.data_ptr(), self.id_off.data_ptr(), self.id_len.data_ptr()
+        return c
+
+
+class DeviceEnvelopeSource:
+    """An EnvelopeSource in device memory (plumbing only): copied with torch, or built from
+    tensors that are already there."""
+
+    def __init__(self, src: "EnvelopeSource", device: int = 0):
+        self.n_msgs, self.flags = src.n_msgs, int(src.flags)
+        for k, a in src.arrays().items():
+            if k in ("bodies", "ids"):
+                setattr(self, k + "_len", int(a.size))
+            setattr(self, k, None if a is None else _to_dev(a, device))
+
+    @classmethod
+    def from_tensors(cls, n_msgs: int, flags: int = 0, **tensors) -> "DeviceEnvelopeSource":
+        self = cls.__new__(cls)
+        self.n_msgs, self.flags = int(n_msgs), int(flags)
+        for k in ("bodies", "ids") + tuple(_ENV_SRC):
+            t = tensors.get(k)
+            setattr(self, k, t)
+            if k in ("bodies", "ids"):
+                setattr(self, k + "_len", 0 if t is None else int(t.numel()))
+        return self
+
+    def to_c(self) -> EnvelopeSource_C:
+        c = EnvelopeSource_C()
+        c.n_msgs, c.flags, c.bodies_len, c.ids_len = self.n_msgs, self.flags, self.bodies_len, self.ids_len
+        for k in ("bodies", "ids") + tuple(_ENV_SRC):
+            t = getattr(self, k)
+            setattr(c, k, None if t is None else t.data_ptr())
+        return c
 
 
 # ---------------------------------------------------------------------------
