@@ -6,44 +6,11 @@
 // again into a buffer of exactly the size asked for: `make envelope_check` builds it with
 // the address and undefined-behaviour sanitizers and runs it, so a read past a frame or a
 // write past a count stops it.  It needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../mochi-db_amd/csrc/envelope.h"
+#include "check_util.h"
 
-static int g_failed = 0;
-#define CHECK(cond, ...)                   \
-  do {                                     \
-    if (!(cond)) {                         \
-      g_failed++;                          \
-      fprintf(stderr, "FAIL %s: ", #cond); \
-      fprintf(stderr, __VA_ARGS__);        \
-      fprintf(stderr, "\n");               \
-    }                                      \
-  } while (0)
-
-using Bytes = std::string;
-
-static Bytes varint(uint64_t v) {
-  Bytes o;
-  while (v >= 0x80) {
-    o.push_back((char)((v & 0x7F) | 0x80));
-    v >>= 7;
-  }
-  o.push_back((char)v);
-  return o;
-}
-static Bytes ld(uint32_t field, const Bytes& p) { return varint(field << 3 | 2) + varint(p.size()) + p; }
-
-template <class T>
-struct Exact {  // a heap array of exactly n elements (never empty: a valid address)
-  T* p;
-  explicit Exact(size_t n) : p((T*)malloc(n ? n * sizeof(T) : 1)) {}
-  ~Exact() { free(p); }
-};
+// a length-delimited field by its number (the payload fields take two tag bytes)
+static Bytes fld(uint32_t field, const Bytes& p) { return ld(field << 3 | 2, p); }
 
 struct Counts {
   uint32_t status[3] = {0, 0, 0};
@@ -54,10 +21,8 @@ static const Bytes kId = "123e4567-e89b-12d3-a456-426614174000";
 
 // `lead` bytes, then the frame, ending the allocation: no byte after the frame is readable
 static void one(const Bytes& frame, size_t lead, Counts& cnt) {
-  const size_t n = lead + frame.size();
-  Exact<uint8_t> wire(n);
-  memset(wire.p, 0x5A, lead);
-  if (frame.size()) memcpy(wire.p + lead, frame.data(), frame.size());
+  const Wire wire(frame, lead);
+  const size_t n = wire.n;
   Exact<uint64_t> f_off(1), b_off(1), s_off(1), m_off(1), r_off(1);
   Exact<uint32_t> f_len(1), b_len(1), s_len(1), m_len(1), r_len(1);
   Exact<uint8_t> st(1), kind(1);
@@ -126,26 +91,20 @@ int main() {
   const Bytes ten = Bytes(9, '\xff') + Bytes("\x01", 1);
   std::vector<Bytes> frames = {
       // a canonical request and a canonical reply
-      Bytes("\x28") + varint(1700000000000ull) + ld(6, "server-1") + ld(7, kId) + ld(107, ld(1, "client") + Bytes("\x18\x07", 2)),
-      Bytes("\x28") + ten + ld(6, "s\xc3\xa9rv-\xe2\x82\xac-\xf0\x9f\x94\x91") + ld(7, "reply-id") + ld(8, kId) + ld(108, ld(1, "grant")),
+      Bytes("\x28") + varint(1700000000000ull) + fld(6, "server-1") + fld(7, kId) + fld(107, fld(1, "client") + Bytes("\x18\x07", 2)),
+      Bytes("\x28") + ten + fld(6, "s\xc3\xa9rv-\xe2\x82\xac-\xf0\x9f\x94\x91") + fld(7, "reply-id") + fld(8, kId) + fld(108, fld(1, "grant")),
       // unknown fields and groups between the known ones, fields out of order, an overlong tag, no payload
-      ld(8, kId) + groups + Bytes("\xBA\x00\x02id", 5) + ld(9, "unknown") + Bytes("\x28\x05", 2) + Bytes("\x65\x01\x02\x03\x04", 5) + ld(6, "s"),
+      fld(8, kId) + groups + Bytes("\xBA\x00\x02id", 5) + fld(9, "unknown") + Bytes("\x28\x05", 2) + Bytes("\x65\x01\x02\x03\x04", 5) + fld(6, "s"),
   };
   Counts cnt;
   for (const Bytes& b : frames) {
-    for (size_t n = 0; n <= b.size(); n++) one(b.substr(0, n), n % 5, cnt);
-    for (size_t i = 0; i < b.size(); i++)
-      for (int bit = 0; bit < 8; bit++) {
-        Bytes m = b;
-        m[i] = (char)(m[i] ^ (1 << bit));
-        one(m, (i + bit) % 4, cnt);
-      }
+    for_mutants(b, [&](const Bytes& m, bool flip, size_t k) { one(m, flip ? k % 4 : k % 5, cnt); });
   }
   one(Bytes(8, '\xff'), 0, cnt);
   // the oneof rule, and a second payload behind a truncated one
-  one(ld(107, "a") + ld(107, "b"), 1, cnt);
-  one(ld(107, "a") + ld(110, "b") + ld(8, kId), 2, cnt);
-  one(ld(107, "a") + ld(108, "b") + Bytes("\x3A\x05id", 4), 3, cnt);
+  one(fld(107, "a") + fld(107, "b"), 1, cnt);
+  one(fld(107, "a") + fld(110, "b") + fld(8, kId), 2, cnt);
+  one(fld(107, "a") + fld(108, "b") + Bytes("\x3A\x05id", 4), 3, cnt);
   for (int s = 0; s < 3; s++) CHECK(cnt.status[s] > 0, "no frame reached status %d", s);
   CHECK(cnt.matched > 0 && cnt.wrapped > 0, "nothing matched or wrapped");
   printf("envelope_check: %llu frames (OK %u, MALFORMED %u, FALLBACK %u), %llu matched, %llu wrapped, %d failures\n",

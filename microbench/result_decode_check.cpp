@@ -5,38 +5,9 @@
 // size, into slot arrays of exactly n_ops entries: `make result_decode_check` builds
 // it with the address and undefined-behaviour sanitizers and runs it, so a read past a
 // body or a write past a slot run stops it.  It needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../mochi-db_amd/csrc/result_decode.h"
+#include "check_util.h"
 
-static int g_failed = 0;
-#define CHECK(cond, ...)                   \
-  do {                                     \
-    if (!(cond)) {                         \
-      g_failed++;                          \
-      fprintf(stderr, "FAIL %s: ", #cond); \
-      fprintf(stderr, __VA_ARGS__);        \
-      fprintf(stderr, "\n");               \
-    }                                      \
-  } while (0)
-
-using Bytes = std::string;
-
-static Bytes varint(uint64_t v) {
-  Bytes o;
-  while (v >= 0x80) {
-    o.push_back((char)((v & 0x7F) | 0x80));
-    v >>= 7;
-  }
-  o.push_back((char)v);
-  return o;
-}
-static Bytes ld(int tag, const Bytes& p) { return Bytes(1, (char)tag) + varint(p.size()) + p; }
-static Bytes entry(int tag, const Bytes& k, const Bytes& v) { return ld(tag, ld(0x0A, k) + ld(0x12, v)); }
 static Bytes grant(const Bytes& oid, uint64_t ts) {
   return ld(0x0A, oid) + "\x10" + varint(ts) + ld(0x22, Bytes(16, 'a')) + Bytes("\x28\x01", 2);
 }
@@ -62,16 +33,14 @@ struct Counts {
 
 // `lead` bytes, then the body, ending the allocation: no byte after the body is readable
 static void decode_one(const Bytes& body, uint8_t kind, uint32_t n_ops, size_t lead, Counts& cnt) {
-  const size_t n = lead + body.size();
-  uint8_t* wire = (uint8_t*)malloc(n ? n : 1);
-  memset(wire, 0x5A, lead);
-  if (body.size()) memcpy(wire + lead, body.data(), body.size());
+  const Wire wire(body, lead);
+  const size_t n = wire.n;
   const uint64_t resp_off[1] = {lead}, slot_off[1] = {0};
   const uint32_t resp_len[1] = {(uint32_t)body.size()}, req_resp_off[2] = {0, 1}, k[1] = {n_ops};
   mochi_result_replies in;
   memset(&in, 0, sizeof in);
   in.n_resps = in.n_reqs = 1;
-  in.wire = wire;
+  in.wire = wire.p;
   in.wire_len = n;
   in.resp_off = resp_off;
   in.resp_len = resp_len;
@@ -121,7 +90,6 @@ static void decode_one(const Bytes& body, uint8_t kind, uint32_t n_ops, size_t l
   cnt.status[st]++;
   cnt.calls++;
   cnt.slots += n_ops;
-  free(wire);
 }
 
 int main() {
@@ -145,13 +113,7 @@ int main() {
   };
   Counts cnt;
   for (const B& b : bodies) {
-    for (size_t n = 0; n <= b.body.size(); n++) decode_one(b.body.substr(0, n), b.kind, b.n_ops, n % 5, cnt);
-    for (size_t i = 0; i < b.body.size(); i++)
-      for (int bit = 0; bit < 8; bit++) {
-        Bytes m = b.body;
-        m[i] = (char)(m[i] ^ (1 << bit));
-        decode_one(m, b.kind, b.n_ops, (i + bit) % 4, cnt);
-      }
+    for_mutants(b.body, [&](const Bytes& m, bool flip, size_t k) { decode_one(m, b.kind, b.n_ops, flip ? k % 4 : k % 5, cnt); });
   }
   decode_one(Bytes(8, '\xff'), MOCHI_RR_READ, 0, 0, cnt);
   decode_one(Bytes(8, '\xff'), MOCHI_RR_OTHER, 3, 1, cnt);

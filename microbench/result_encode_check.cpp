@@ -9,37 +9,9 @@
 // the encoder asks for: `make result_encode_check` builds it with the address and
 // undefined-behaviour sanitizers and runs it, so a read past a body, a slice past a blob
 // or a write past the wire stops it.  It needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../mochi-db_amd/csrc/result_encode.h"
+#include "check_util.h"
 
-static int g_failed = 0;
-#define CHECK(cond, ...)                   \
-  do {                                     \
-    if (!(cond)) {                         \
-      g_failed++;                          \
-      fprintf(stderr, "FAIL %s: ", #cond); \
-      fprintf(stderr, __VA_ARGS__);        \
-      fprintf(stderr, "\n");               \
-    }                                      \
-  } while (0)
-
-using Bytes = std::string;
-
-static Bytes varint(uint64_t v) {
-  Bytes o;
-  while (v >= 0x80) {
-    o.push_back((char)((v & 0x7F) | 0x80));
-    v >>= 7;
-  }
-  o.push_back((char)v);
-  return o;
-}
-static Bytes ld(int tag, const Bytes& p) { return Bytes(1, (char)tag) + varint(p.size()) + p; }
 static Bytes operation(int action, const Bytes& key, const Bytes& value, const Bytes& raw = "") {
   return (action ? Bytes("\x08") + varint(action) : "") + ld(0x12, key) + (value.empty() ? "" : ld(0x1A, value)) + raw;
 }
@@ -51,10 +23,9 @@ struct Counts {
 
 // `lead` bytes, then the body, ending the allocation: no byte after the body is readable
 static void plan_and_encode(const Bytes& body, uint32_t k, size_t lead, Counts& cnt) {
-  const size_t n = lead + body.size();
-  uint8_t* wire = (uint8_t*)malloc(n ? n : 1);
-  memset(wire, 0x5A, lead);
-  if (body.size()) memcpy(wire + lead, body.data(), body.size());
+  const Wire wire_buf(body, lead);
+  uint8_t* const wire = wire_buf.p;
+  const size_t n = wire_buf.n;
   const uint64_t msg_off[1] = {lead}, slot_off[1] = {0};
   const uint32_t msg_len[1] = {(uint32_t)body.size()}, flags_off[2] = {0, k}, accept[1] = {1};
   const uint8_t msg_status[1] = {MOCHI_MSG_OK};
@@ -69,7 +40,8 @@ static void plan_and_encode(const Bytes& body, uint32_t k, size_t lead, Counts& 
   // the store: per op a value and a certificate, in a heap blob of exactly their size
   const Bytes value = "stored", cert = ld(0x7A, "stored-certificate");
   const size_t store_len = (value.size() + cert.size()) * k;
-  uint8_t* store = (uint8_t*)malloc(store_len ? store_len : 1);
+  const Exact<uint8_t> store_buf(store_len);
+  uint8_t* const store = store_buf.p;
   std::vector<uint8_t> dec(k), sfl(k);
   std::vector<uint64_t> v_off(k), c_off(k);
   std::vector<uint32_t> v_len(k), c_len(k);
@@ -155,17 +127,15 @@ static void plan_and_encode(const Bytes& body, uint32_t k, size_t lead, Counts& 
   CHECK(plan == MOCHI_W2A_REPLY ? (rc == MOCHI_EINVAL && need >= 2) : (rc == MOCHI_OK && need == 0), "sizing: rc %d need %llu (%s)",
         rc, (unsigned long long)need, err);
   if (need) {
-    uint8_t* out = (uint8_t*)malloc(need);
+    const Exact<uint8_t> out_buf(need);
+    uint8_t* const out = out_buf.p;
     rc = mochi_host::result_reply_encode(&a, out, need, &off, &len, &st, &need2, &err);
     CHECK(rc == MOCHI_OK && need2 == need && len == need && st == MOCHI_ENC_OK && out[0] == 0x0A, "encode: rc %d (%s)", rc, err);
-    free(out);
   }
   cnt.plan[plan]++;
   cnt.calls++;
   cnt.slots += k;
   cnt.bytes += need;
-  free(store);
-  free(wire);
 }
 
 int main() {
@@ -190,13 +160,7 @@ int main() {
   };
   Counts cnt;
   for (const B& b : bodies) {
-    for (size_t n = 0; n <= b.body.size(); n++) plan_and_encode(b.body.substr(0, n), b.k, n % 5, cnt);
-    for (size_t i = 0; i < b.body.size(); i++)
-      for (int bit = 0; bit < 8; bit++) {
-        Bytes m = b.body;
-        m[i] = (char)(m[i] ^ (1 << bit));
-        plan_and_encode(m, b.k, (i + bit) % 4, cnt);
-      }
+    for_mutants(b.body, [&](const Bytes& m, bool flip, size_t k) { plan_and_encode(m, b.k, flip ? k % 4 : k % 5, cnt); });
   }
   plan_and_encode("", 0, 0, cnt);
   plan_and_encode(Bytes(8, '\xff'), 2, 1, cnt);

@@ -4,39 +4,11 @@
 // three reply bodies is decoded from a heap buffer of exactly its size, into output
 // arrays of exactly the sizes the call asks for: `make w1_decode_check` builds it with
 // the address and undefined-behaviour sanitizers and runs it, so a read past a body or
-// a write past a count stops it.  It needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
+// a write past a count stops it.  A second block runs the Grant parser of
+// csrc/wire_walk.h alone over a grant corpus.  It needs no GPU.
 #include "../mochi-db_amd/csrc/w1_decode.h"
+#include "check_util.h"
 
-static int g_failed = 0;
-#define CHECK(cond, ...)                   \
-  do {                                     \
-    if (!(cond)) {                         \
-      g_failed++;                          \
-      fprintf(stderr, "FAIL %s: ", #cond); \
-      fprintf(stderr, __VA_ARGS__);        \
-      fprintf(stderr, "\n");               \
-    }                                      \
-  } while (0)
-
-using Bytes = std::string;
-
-static Bytes varint(uint64_t v) {
-  Bytes o;
-  while (v >= 0x80) {
-    o.push_back((char)((v & 0x7F) | 0x80));
-    v >>= 7;
-  }
-  o.push_back((char)v);
-  return o;
-}
-static Bytes ld(int tag, const Bytes& p) { return Bytes(1, (char)tag) + varint(p.size()) + p; }
-static Bytes entry(int tag, const Bytes& k, const Bytes& v) { return ld(tag, ld(0x0A, k) + ld(0x12, v)); }
 static Bytes grant(const Bytes& oid, uint64_t ts, int status = 0) {
   return ld(0x0A, oid) + "\x10" + varint(ts) + ld(0x22, Bytes(32, 'a')) + (status ? Bytes("\x28") + varint(status) : "");
 }
@@ -68,10 +40,7 @@ static void decode_one(const Bytes& body, uint8_t kind, Counts& cnt) {
   const Bytes ids = "server-0server-1";
   const uint32_t id_off[3] = {0, 8, 16};
   const Bytes strings = "alphabeta";
-  uint8_t* wire = (uint8_t*)malloc(body.size());  // exact: no byte after the body is readable
-  if (body.size()) memcpy(wire, body.data(), body.size());
-  uint8_t* str = (uint8_t*)malloc(strings.size());
-  memcpy(str, strings.data(), strings.size());
+  const Wire wire(body), str(strings);  // exact: no byte after the body is readable
   const uint64_t resp_off[1] = {0}, op_key_off[2] = {0, 5};
   const uint32_t resp_len[1] = {(uint32_t)body.size()}, req_resp_off[2] = {0, 1}, req_op_off[2] = {0, 2},
                  op_key_len[2] = {5, 4};
@@ -80,13 +49,13 @@ static void decode_one(const Bytes& body, uint8_t kind, Counts& cnt) {
   in.n_resps = 1;
   in.n_reqs = 1;
   in.n_ops = 2;
-  in.wire = wire;
+  in.wire = wire.p;
   in.wire_len = body.size();
   in.resp_off = resp_off;
   in.resp_len = resp_len;
   in.resp_kind = &kind;
   in.req_resp_off = req_resp_off;
-  in.strings = str;
+  in.strings = str.p;
   in.strings_len = strings.size();
   in.req_op_off = req_op_off;
   in.op_key_off = op_key_off;
@@ -140,11 +109,40 @@ static void decode_one(const Bytes& body, uint8_t kind, Counts& cnt) {
   cnt.calls++;
   cnt.grants += N;
   cnt.certs += C;
-  free(wire);
-  free(str);
+}
+
+// wire::parse_grant alone (the Grant parser of this decoder and of the host Write2
+// encoder), over every truncation and bit flip of three grants -- the demo grant; one
+// with multi-byte UTF-8, all five fields, fixed32 / fixed64 unknowns and a second
+// objectId; one with unknown groups nested 1, 15, 16 and 17 deep -- and over groups
+// nested 99, 100 and 101 deep: each grant ends an exact-size heap buffer.
+static Bytes groups(int depth) { return Bytes(depth, '\x4b') + Bytes(depth, '\x4c'); }
+static void grant_corpus() {
+  const Bytes utf8 = "k\xc3\xa9y-\xe2\x82\xac-\xf0\x9f\x94\x91";
+  const std::vector<Bytes> grants = {
+      ld(0x0A, "DEMO_KEY_1") + "\x10" + varint(1342) + ld(0x22, Bytes(128, 'a')),
+      ld(0x0A, utf8) + "\x10" + varint(1700000000000ull) + Bytes("\x18\x07", 2) + ld(0x22, "h\xc3\xa4sh" + Bytes(27, 'b')) +
+          Bytes("\x28\x01", 2) + Bytes("\x4d\x01\x02\x03\x04", 5) + Bytes("\x49\x01\x02\x03\x04\x05\x06\x07\x08", 9) +
+          ld(0x0A, "second"),
+      ld(0x0A, "grp") + groups(1) + groups(15) + groups(16) + groups(17) + Bytes("\x10\x05", 2),
+  };
+  uint32_t n = 0, ok = 0;
+  auto one = [&](const Bytes& m, size_t lead) {
+    const Wire w(m, lead);
+    mochi::wire::Grant g;
+    n++;
+    if (!mochi::wire::parse_grant(w.p, (uint32_t)lead, (uint32_t)m.size(), g)) return;
+    ok++;
+    CHECK(g.oid_len == 0 || (g.oid_off >= lead && g.oid_off + g.oid_len <= w.n), "objectId outside the grant");
+  };
+  for (const Bytes& b : grants) for_mutants(b, [&](const Bytes& m, bool flip, size_t k) { one(m, flip ? k % 4 : k % 5); });
+  for (int d = 99; d <= 101; d++) one(ld(0x0A, "deep") + groups(d), d % 4);
+  CHECK(ok > 0 && ok < n, "grants accepted: %u of %u", ok, n);
+  printf("w1_decode_check: %u grants through wire::parse_grant, %u accepted\n", n, ok);
 }
 
 int main() {
+  grant_corpus();
   const Bytes g1 = grant("alpha", 11), g2 = grant("beta", 12, 1);
   std::vector<Bytes> bodies = {
       ld(0x0A, multigrant({{"alpha", g1}}, "server-1", true)) + entry(0x12, "alpha", writecert("alpha")),
@@ -158,13 +156,9 @@ int main() {
   };
   Counts cnt;
   for (const Bytes& b : bodies) {
-    for (size_t n = 0; n <= b.size(); n++) decode_one(b.substr(0, n), MOCHI_W1_OK, cnt);
-    for (size_t i = 0; i < b.size(); i++)
-      for (int bit = 0; bit < 8; bit++) {
-        Bytes m = b;
-        m[i] = (char)(m[i] ^ (1 << bit));
-        decode_one(m, (i + bit) % 2 ? MOCHI_W1_OK : MOCHI_W1_REFUSED, cnt);
-      }
+    for_mutants(b, [&](const Bytes& m, bool flip, size_t k) {
+      decode_one(m, !flip || k % 2 ? MOCHI_W1_OK : MOCHI_W1_REFUSED, cnt);
+    });
   }
   decode_one(Bytes(8, '\xff'), MOCHI_W1_OK, cnt);
   decode_one(bodies[0], MOCHI_W1_REQUEST_FAILED, cnt);

@@ -5,37 +5,9 @@
 // size, into output arrays of exactly the sizes the call asks for: `make
 // w1_request_check` builds it with the address and undefined-behaviour sanitizers and
 // runs it, so a read past a body or a write past a count stops it.  It needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../mochi-db_amd/csrc/w1_request.h"
+#include "check_util.h"
 
-static int g_failed = 0;
-#define CHECK(cond, ...)                   \
-  do {                                     \
-    if (!(cond)) {                         \
-      g_failed++;                          \
-      fprintf(stderr, "FAIL %s: ", #cond); \
-      fprintf(stderr, __VA_ARGS__);        \
-      fprintf(stderr, "\n");               \
-    }                                      \
-  } while (0)
-
-using Bytes = std::string;
-
-static Bytes varint(uint64_t v) {
-  Bytes o;
-  while (v >= 0x80) {
-    o.push_back((char)((v & 0x7F) | 0x80));
-    v >>= 7;
-  }
-  o.push_back((char)v);
-  return o;
-}
-static Bytes ld(int tag, const Bytes& p) { return Bytes(1, (char)tag) + varint(p.size()) + p; }
 static Bytes op(uint64_t action, const Bytes& o1, const Bytes& o2 = "", const Bytes& o3 = "") {
   return (action ? Bytes("\x08") + varint(action) : Bytes()) + (o1.empty() ? "" : ld(0x12, o1)) +
          (o2.empty() ? "" : ld(0x1A, o2)) + (o3.empty() ? "" : ld(0x22, o3));
@@ -48,16 +20,14 @@ struct Counts {
 
 // `lead` bytes, then the body, ending the allocation: no byte after the body is readable
 static void decode_one(const Bytes& body, size_t lead, Counts& cnt) {
-  const size_t n = lead + body.size();
-  uint8_t* wire = (uint8_t*)malloc(n ? n : 1);
-  memset(wire, 0x5A, lead);
-  if (body.size()) memcpy(wire + lead, body.data(), body.size());
+  const Wire wire(body, lead);
+  const size_t n = wire.n;
   const uint64_t msg_off[1] = {lead};
   const uint32_t msg_len[1] = {(uint32_t)body.size()};
   mochi_write1_requests in;
   memset(&in, 0, sizeof in);
   in.n_reqs = 1;
-  in.wire = wire;
+  in.wire = wire.p;
   in.wire_len = n;
   in.msg_off = msg_off;
   in.msg_len = msg_len;
@@ -100,7 +70,6 @@ static void decode_one(const Bytes& body, size_t lead, Counts& cnt) {
   cnt.calls++;
   cnt.ops += O;
   cnt.keys += out.n_keys;
-  free(wire);
 }
 
 int main() {
@@ -118,13 +87,7 @@ int main() {
   };
   Counts cnt;
   for (const Bytes& b : bodies) {
-    for (size_t n = 0; n <= b.size(); n++) decode_one(b.substr(0, n), n % 5, cnt);
-    for (size_t i = 0; i < b.size(); i++)
-      for (int bit = 0; bit < 8; bit++) {
-        Bytes m = b;
-        m[i] = (char)(m[i] ^ (1 << bit));
-        decode_one(m, (i + bit) % 4, cnt);
-      }
+    for_mutants(b, [&](const Bytes& m, bool flip, size_t k) { decode_one(m, flip ? k % 4 : k % 5, cnt); });
   }
   decode_one(Bytes(8, '\xff'), 0, cnt);
   // the shapes validated whole: a second transaction, 65 operations (the last one cut short too)

@@ -22,6 +22,7 @@
 #include "w1_issue.h"
 #include "w1_reply.h"
 #include "w1_request.h"
+#include "wire_walk.h"
 
 using namespace mochi;
 
@@ -817,7 +818,7 @@ int check_write1_replies(const mochi_write1_replies* r, const mochi_write1_decod
   if (r->n_reqs && (!r->req_resp_off || !r->req_op_off)) return fail(MOCHI_EINVAL, "req_resp_off / req_op_off required");
   if (r->n_ops && (!r->op_key_off || !r->op_key_len || (!r->strings && r->strings_len)))
     return fail(MOCHI_EINVAL, "strings / op_key_off / op_key_len required");
-  if (r->n_resps > mochi::w1d::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
+  if (r->n_resps > mochi::wire::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
   if (o->grant_cap && (!o->grant_off || !o->grant_len || !o->grant_key || !o->grant_ts || !o->grant_status ||
                        !o->grant_flags))
     return fail(MOCHI_EINVAL, "the per-grant outputs are required (grant_cap > 0)");
@@ -1769,7 +1770,7 @@ namespace {
 
 int check_result_replies(const mochi_result_replies* r, const mochi_result_decoded* o) {
   if (!r || !o) return fail(MOCHI_EINVAL, "null argument");
-  if (r->n_resps > mochi::w1d::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
+  if (r->n_resps > mochi::wire::kMaxResps) return fail(MOCHI_EINVAL, "more than 2^24 responses");
   if (!r->n_resps) return MOCHI_OK;
   if (!r->n_reqs) return fail(MOCHI_EINVAL, "responses without a request");
   if (!r->resp_off || !r->resp_len || !r->resp_kind || (!r->wire && r->wire_len))

@@ -5,25 +5,26 @@
 //
 // Everything under `namespace env` is __host__ __device__ and reads a frame through
 // (base pointer, offsets below the frame length) alone, with the field walk of
-// w1_decode.h (w1d::next_fld and friends): the host form and every kernel run the
+// wire_walk.h (wire::next_fld and friends): the host form and every kernel run the
 // same walk over the same bytes, and a stand-alone host program
 // (microbench/envelope_check.cpp) checks under a sanitizer that no read leaves the
 // slice.
 //
 // Wire layout (MochiProtocol.proto:194-213), parsed as protobuf-java 3.16.3 parses it
-// (the rules of w1_decode.h) and written as it writes it:
+// (the rules of wire_walk.h) and written as it writes it:
 //   ProtocolMessage = [28 msgTimestamp] [32 serverId] [3A msgId] [42 replyToMsgId]
 //                     [payload: field 101..112, length-delimited]
 #pragma once
-#include "w1_decode.h"
+#include "carve.h"
 #include "w2_encode.h"
+#include "wire_walk.h"
 
 namespace mochi {
 namespace env {
 
-using w1d::Fld;
-using w1d::next_fld;
-using w1d::valid_utf8;
+using wire::Fld;
+using wire::next_fld;
+using wire::valid_utf8;
 
 constexpr uint32_t kMaxFrames = 1u << 24;
 constexpr uint32_t kKinds = 13;  // PAYLOAD_NOT_SET and the cases 101..112
@@ -38,7 +39,7 @@ struct Top {
 // Returns enum mochi_env_status.  Unless it is OK nothing of `o` is to be used.  The
 // envelope level is validated whole before the oneof rule is applied: a frame with two
 // payload fields whose own framing or strings are bad is MALFORMED, not FALLBACK.
-W1D_HD uint32_t frame_level(const uint8_t* p, uint32_t len, Top& o) {
+WIRE_HD uint32_t frame_level(const uint8_t* p, uint32_t len, Top& o) {
   o.kind = o.body_off = o.body_len = 0;
   o.ts = 0;
   o.sid_off = o.sid_len = o.mid_off = o.mid_len = o.rto_off = o.rto_len = 0;
@@ -76,7 +77,7 @@ struct DecView {
   mochi_envelope_frames in;
   mochi_envelope_decoded out;
 };
-W1D_HD void decode_frame(const DecView& v, uint32_t f) {
+WIRE_HD void decode_frame(const DecView& v, uint32_t f) {
   const uint64_t base = v.in.frame_off[f];
   Top t;
   const uint32_t st = frame_level(v.in.wire + base, v.in.frame_len[f], t);
@@ -97,7 +98,7 @@ W1D_HD void decode_frame(const DecView& v, uint32_t f) {
 
 // ---- route -----------------------------------------------------------------------------
 // the bin of a frame: its kind, or kKinds for a frame that takes no place
-W1D_HD uint32_t route_bin(uint8_t status, uint8_t kind) {
+WIRE_HD uint32_t route_bin(uint8_t status, uint8_t kind) {
   return status == MOCHI_ENV_OK && kind < kKinds ? (uint32_t)kind : kKinds;
 }
 struct RouteView {
@@ -111,7 +112,7 @@ struct RouteView {
 
 // ---- join -------------------------------------------------------------------------------
 // The msgId table is k_w1q_claim's (w1_request.hip): open addressing, the slot from
-// w1d::bytes_hash, the smallest claimant wins.  Its slots: a power of two, at least 2 * Q
+// wire::bytes_hash, the smallest claimant wins.  Its slots: a power of two, at least 2 * Q
 inline uint32_t join_slots(uint32_t Q) {
   uint32_t s = 16;
   while (s < 2 * (uint64_t)Q) s <<= 1;
@@ -123,10 +124,10 @@ inline int join_key_bits(uint32_t Q) {
   while (b < 32 && (Q >> b)) b++;
   return b;
 }
-W1D_HD uint8_t w1_kind_of(uint8_t kind) {
+WIRE_HD uint8_t w1_kind_of(uint8_t kind) {
   return kind == 8 ? MOCHI_W1_OK : kind == 9 ? MOCHI_W1_REFUSED : kind == 12 ? MOCHI_W1_REQUEST_FAILED : MOCHI_W1_OTHER;
 }
-W1D_HD uint8_t rr_kind_of(uint8_t kind) {
+WIRE_HD uint8_t rr_kind_of(uint8_t kind) {
   return kind == 11 ? MOCHI_RR_WRITE2_ANS : kind == 6 ? MOCHI_RR_READ : MOCHI_RR_OTHER;
 }
 struct JoinView {
@@ -136,9 +137,9 @@ struct JoinView {
   mochi_envelope_joined out;
 };
 // does frame f look for a request at all
-W1D_HD bool join_asks(const JoinView& v, uint32_t f) { return v.dec.status[f] == MOCHI_ENV_OK && v.dec.reply_to_len[f] != 0; }
+WIRE_HD bool join_asks(const JoinView& v, uint32_t f) { return v.dec.status[f] == MOCHI_ENV_OK && v.dec.reply_to_len[f] != 0; }
 // slot i of the grouped outputs <- frame f
-W1D_HD void join_emit(const JoinView& v, uint32_t i, uint32_t f) {
+WIRE_HD void join_emit(const JoinView& v, uint32_t i, uint32_t f) {
   const uint8_t k = v.dec.kind[f];
   v.out.resp_frame[i] = f;
   v.out.resp_off[i] = v.dec.body_off[f];
@@ -148,13 +149,13 @@ W1D_HD void join_emit(const JoinView& v, uint32_t i, uint32_t f) {
 }
 
 // ---- wrap: sizes ------------------------------------------------------------------------
-W1D_HD uint32_t len_or_0(const uint64_t* off, const uint32_t* len, uint32_t m) { return off ? len[m] : 0; }
+WIRE_HD uint32_t len_or_0(const uint64_t* off, const uint32_t* len, uint32_t m) { return off ? len[m] : 0; }
 struct Sized {
   uint64_t len;     // the message; 0 unless status is OK
   uint32_t prefix;  // bytes of the length prefix before it (0 without MOCHI_ENV_LENGTH_PREFIX)
   uint8_t status;
 };
-W1D_HD Sized size_msg(const mochi_envelope_source& s, uint32_t m) {
+WIRE_HD Sized size_msg(const mochi_envelope_source& s, uint32_t m) {
   Sized z{0, 0, MOCHI_ENC_OK};
   const uint8_t k = s.kind[m];
   if (k >= kKinds) {
@@ -167,8 +168,8 @@ W1D_HD Sized size_msg(const mochi_envelope_source& s, uint32_t m) {
       z.status = MOCHI_ENC_BAD_ID;
     } else {
       const uint64_t ts = (uint64_t)s.msg_timestamp[m];
-      z.len = (ts ? 1 + enc_varint_size(ts) : 0) + enc_ld_opt_size(sl) + enc_ld_opt_size(ml) + enc_ld_opt_size(rl) +
-              (k ? 2 + enc_varint_size(s.body_len[m]) + (uint64_t)s.body_len[m] : 0);  // the payload tag takes two bytes
+      z.len = (ts ? 1 + wire::varint_size(ts) : 0) + enc_ld_opt_size(sl) + enc_ld_opt_size(ml) + enc_ld_opt_size(rl) +
+              (k ? 2 + wire::varint_size(s.body_len[m]) + (uint64_t)s.body_len[m] : 0);  // the payload tag takes two bytes
       if (z.len > kEncMaxMsg) {
         z.status = MOCHI_ENC_TOO_LONG;
         z.len = 0;
@@ -176,11 +177,11 @@ W1D_HD Sized size_msg(const mochi_envelope_source& s, uint32_t m) {
     }
   }
   // a message that is not OK is emitted empty; with the prefix flag its frame is the one byte 00
-  z.prefix = s.flags & MOCHI_ENV_LENGTH_PREFIX ? enc_varint_size(z.len) : 0;
+  z.prefix = s.flags & MOCHI_ENV_LENGTH_PREFIX ? wire::varint_size(z.len) : 0;
   return z;
 }
 // the two tag bytes of payload case k (1..12): field 100 + k, length-delimited
-W1D_HD uint32_t payload_tag(uint32_t k) { return ((100 + k) << 3) | 2; }
+WIRE_HD uint32_t payload_tag(uint32_t k) { return ((100 + k) << 3) | 2; }
 
 }  // namespace env
 

@@ -101,12 +101,12 @@ __global__ __launch_bounds__(256) void k_env_claim(EnvJoinArgs a) {
   const uint32_t kl = rq.id_len[q], mask = a.slots - 1;
   if (!kl) return;  // an empty id is matched by nothing
   const uint8_t* k = rq.ids + rq.id_off[q];
-  uint32_t h = w1d::bytes_hash(k, kl) & mask;
+  uint32_t h = wire::bytes_hash(k, kl) & mask;
   // at most Q ids in >= 2 * Q slots: a free or equal slot is met within `mask` steps
 #pragma unroll 1
   for (uint32_t n = 0; n <= mask; n++, h = (h + 1) & mask) {
     const uint32_t prev = atomicCAS(&a.tbl_req[h], kNone, q);
-    if (prev == kNone || prev == q || (rq.id_len[prev] == kl && w1d::bytes_eq(rq.ids + rq.id_off[prev], k, kl))) {
+    if (prev == kNone || prev == q || (rq.id_len[prev] == kl && wire::bytes_eq(rq.ids + rq.id_off[prev], k, kl))) {
       atomicMin(&a.tbl_min[h], q);
       break;
     }
@@ -121,12 +121,12 @@ __global__ __launch_bounds__(256) void k_env_lookup(EnvJoinArgs a) {
   if (join_asks(a.v, f)) {
     const uint32_t kl = a.v.dec.reply_to_len[f], mask = a.slots - 1;
     const uint8_t* k = a.v.fr.wire + a.v.dec.reply_to_off[f];
-    uint32_t h = w1d::bytes_hash(k, kl) & mask;
+    uint32_t h = wire::bytes_hash(k, kl) & mask;
 #pragma unroll 1
     for (uint32_t n = 0; n <= mask; n++, h = (h + 1) & mask) {
       const uint32_t c = a.tbl_req[h];
       if (c == kNone) break;  // the probe chain of this id ends here: no request has it
-      if (rq.id_len[c] == kl && w1d::bytes_eq(rq.ids + rq.id_off[c], k, kl)) {
+      if (rq.id_len[c] == kl && wire::bytes_eq(rq.ids + rq.id_off[c], k, kl)) {
         q = a.tbl_min[h];
         break;
       }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void k_env_hdr(mochi_envelope_source s, const 
   const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= s.n_msgs) return;
   const uint32_t len = msg_len[m];
-  const uint32_t prefix = s.flags & MOCHI_ENV_LENGTH_PREFIX ? enc_varint_size(len) : 0;
+  const uint32_t prefix = s.flags & MOCHI_ENV_LENGTH_PREFIX ? wire::varint_size(len) : 0;
   msg_off[m] = frm_off[m] + prefix;
   uint64_t dst = ~0ull;
   if (*total <= wire_cap) {

@@ -119,7 +119,7 @@ int envelope_encode(const mochi_envelope_source* s, uint8_t* wire, uint64_t wire
   if (total > wire_cap) return bad("wire_cap is smaller than the encoded size (*wire_len)");
   for (uint32_t m = 0; m < M; m++) {
     uint8_t* o = wire + msg_off[m];
-    if (s->flags & MOCHI_ENV_LENGTH_PREFIX) put_varint(o - enc_varint_size(msg_len[m]), msg_len[m]);
+    if (s->flags & MOCHI_ENV_LENGTH_PREFIX) put_varint(o - wire::varint_size(msg_len[m]), msg_len[m]);
     if (status[m] != MOCHI_ENC_OK) continue;
     const uint64_t ts = (uint64_t)s->msg_timestamp[m];
     if (ts) {

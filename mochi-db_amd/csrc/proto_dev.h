@@ -49,11 +49,13 @@ struct ByteReader {
 constexpr int kMaxGroupDepth = 16;    // register-resident group stack of the fast path
 constexpr int kDeepGroupDepth = 100;  // CodedInputStream's default recursion limit (protobuf-java)
 
-__device__ __forceinline__ bool rd_varint(ByteReader& r, uint32_t& pos, uint64_t& v) {
+// The one varint over a ByteReader, ending at `end` <= r.len.  (The pointer walk
+// of the other codecs, wire_walk.h, states the same rules over plain bytes.)
+__device__ __forceinline__ bool vint(ByteReader& r, uint32_t& pos, uint32_t end, uint64_t& v) {
   uint64_t x = 0;
 #pragma unroll 1
   for (int i = 0; i < 10; i++) {
-    if (pos >= r.len) return false;
+    if (pos >= end) return false;
     const uint32_t c = r.at(pos++);
     x |= (uint64_t)(c & 0x7F) << (7 * i);
     if (!(c & 0x80)) {
@@ -63,6 +65,17 @@ __device__ __forceinline__ bool rd_varint(ByteReader& r, uint32_t& pos, uint64_t
   }
   return false;
 }
+
+__device__ __forceinline__ bool vlen(ByteReader& r, uint32_t& pos, uint32_t end, uint32_t& len) {
+  uint64_t l;
+  if (!vint(r, pos, end, l)) return false;
+  const int32_t l32 = (int32_t)(uint32_t)l;  // readRawVarint32
+  if (l32 < 0 || (uint32_t)l32 > end - pos) return false;
+  len = (uint32_t)l32;
+  return true;
+}
+
+__device__ __forceinline__ bool rd_varint(ByteReader& r, uint32_t& pos, uint64_t& v) { return vint(r, pos, r.len, v); }
 
 __device__ inline bool valid_utf8(ByteReader& r, uint32_t off, uint32_t n) {
   uint32_t i = 0;

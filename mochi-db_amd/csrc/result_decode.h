@@ -6,14 +6,15 @@
 // (mochi_result_replies / mochi_result_decoded).
 //
 // Everything under `namespace rrd` is __host__ __device__, built on the field
-// walk of w1_decode.h (vint, vlen, next_fld, skip_group, valid_utf8,
-// valid_writecert, status_u8) and reads a body through (base pointer, offsets
-// below the body length) alone.  The host form and every kernel call the same
-// functions in the same phases; microbench/result_decode_check.cpp runs them
-// under a sanitizer.
+// walk of wire_walk.h (next_fld, valid_utf8, status_u8) and reads a body
+// through (base pointer, offsets below the body length) alone.  It includes
+// w1_decode.h for one Write1 structure it really decodes: an OperationResult's
+// currentCertificate is a WriteCertificate, validated by w1d::valid_writecert.
+// The host form and every kernel call the same functions in the same phases;
+// microbench/result_decode_check.cpp runs them under a sanitizer.
 //
 // Wire layout (MochiProtocol.proto:45-60, 82-87, 102-105), parsed as
-// protobuf-java 3.16.3 parses it (the rules of w1_decode.h):
+// protobuf-java 3.16.3 parses it (the rules of wire_walk.h):
 //   Write2AnsFromServer = [0A TransactionResult] [12 rid]
 //   ReadFromServer      = [0A TransactionResult] [12 nonce] [1A rid]
 //   TransactionResult   = { 0A OperationResult }
@@ -24,21 +25,21 @@
 namespace mochi {
 namespace rrd {
 
-using w1d::Fld;
-using w1d::kStFb;
-using w1d::kStMal;
-using w1d::next_fld;
-using w1d::status_u8;
-using w1d::valid_utf8;
 using w1d::valid_writecert;
+using wire::Fld;
+using wire::kStFb;
+using wire::kStMal;
+using wire::next_fld;
+using wire::status_u8;
+using wire::valid_utf8;
 
 constexpr uint32_t kMaxOps = MOCHI_MAX_OPS_PER_CERT;
 constexpr uint32_t kUndecoded = 0xFFFFFFFFu;  // resp_n_ops of a MALFORMED / FALLBACK response: equals no n_ops
 
 // is a response of this kind parsed at all
-W1D_HD bool parsed_kind(uint8_t kind) { return kind == MOCHI_RR_WRITE2_ANS || kind == MOCHI_RR_READ; }
+WIRE_HD bool parsed_kind(uint8_t kind) { return kind == MOCHI_RR_WRITE2_ANS || kind == MOCHI_RR_READ; }
 // top-level string fields: 2 in both kinds (rid / nonce), 3 in a ReadFromServer alone (rid)
-W1D_HD bool top_string(uint8_t kind, uint32_t field) { return field == 2 || (field == 3 && kind == MOCHI_RR_READ); }
+WIRE_HD bool top_string(uint8_t kind, uint32_t field) { return field == 2 || (field == 3 && kind == MOCHI_RR_READ); }
 
 // One OperationResult, validated all the way down.  Slices are offsets in the
 // body; an absent field gives the operation's own offset and length 0.
@@ -48,7 +49,7 @@ struct Op {
   int32_t status;   // readEnum: the low 32 bits
   bool existed;     // readBool: any non-zero varint
 };
-W1D_HD bool read_op(const uint8_t* p, uint32_t off, uint32_t len, Op& o) {
+WIRE_HD bool read_op(const uint8_t* p, uint32_t off, uint32_t len, Op& o) {
   o.res_off = o.cert_off = off;
   o.res_len = o.cert_len = o.n_cert = 0;
   o.status = 0;
@@ -77,7 +78,7 @@ W1D_HD bool read_op(const uint8_t* p, uint32_t off, uint32_t len, Op& o) {
 }
 
 // every OperationResult of a TransactionResult value
-W1D_HD bool valid_txresult(const uint8_t* p, uint32_t off, uint32_t len) {
+WIRE_HD bool valid_txresult(const uint8_t* p, uint32_t off, uint32_t len) {
   uint32_t pos = off;
   const uint32_t end = off + len;
   Fld f;
@@ -90,7 +91,7 @@ W1D_HD bool valid_txresult(const uint8_t* p, uint32_t off, uint32_t len) {
 }
 
 // a whole answer body (the shapes level 1 declines are validated here by its lane)
-W1D_HD bool valid_answer(const uint8_t* p, uint32_t len, uint8_t kind) {
+WIRE_HD bool valid_answer(const uint8_t* p, uint32_t len, uint8_t kind) {
   uint32_t pos = 0;
   Fld f;
   int rc;
@@ -110,7 +111,7 @@ struct Level1 {
 };
 // Returns status bits; with bits set only they are to be used.  A response with
 // more than kMaxOps entries is validated whole here and keeps its count.
-W1D_HD uint32_t resp_level(const uint8_t* p, uint32_t len, uint8_t kind, Level1& o) {
+WIRE_HD uint32_t resp_level(const uint8_t* p, uint32_t len, uint8_t kind, Level1& o) {
   o.tr_off = o.tr_len = o.n_wire = o.rid_off = o.rid_len = o.nonce_off = o.nonce_len = 0;
   uint32_t n_res = 0, pos = 0;
   Fld f;
@@ -143,10 +144,10 @@ W1D_HD uint32_t resp_level(const uint8_t* p, uint32_t len, uint8_t kind, Level1&
   return 0;
 }
 // operations a response hands to level 3 (the rest was validated by level 1's lane)
-W1D_HD uint32_t level3_ops(uint32_t bits, uint32_t n_wire) { return bits || n_wire > kMaxOps ? 0u : n_wire; }
+WIRE_HD uint32_t level3_ops(uint32_t bits, uint32_t n_wire) { return bits || n_wire > kMaxOps ? 0u : n_wire; }
 
 // payload slice of the j-th OperationResult of the TransactionResult level 1 accepted
-W1D_HD void op_entry(const uint8_t* p, uint32_t tr_off, uint32_t tr_len, uint32_t j, uint32_t& off, uint32_t& len) {
+WIRE_HD void op_entry(const uint8_t* p, uint32_t tr_off, uint32_t tr_len, uint32_t j, uint32_t& off, uint32_t& len) {
   uint32_t pos = tr_off, i = 0;
   Fld f;
   off = len = 0;
@@ -166,7 +167,7 @@ struct View {
   mochi_result_decoded out;
 };
 
-W1D_HD void slot_absent(const mochi_result_decoded& out, uint64_t s) {
+WIRE_HD void slot_absent(const mochi_result_decoded& out, uint64_t s) {
   out.op_status[s] = 0xFF;
   out.op_existed[s] = 0;
   out.op_flags[s] = 0;
@@ -178,7 +179,7 @@ W1D_HD void slot_absent(const mochi_result_decoded& out, uint64_t s) {
 
 // ---- level 3, per OperationResult j of response p (n_ops: its request's count) ----
 // Validates the operation; writes its slot if it has one.  Returns status bits.
-W1D_HD uint32_t op_level(const View& v, uint32_t p, uint32_t tr_off, uint32_t tr_len, uint32_t j, uint32_t n_ops) {
+WIRE_HD uint32_t op_level(const View& v, uint32_t p, uint32_t tr_off, uint32_t tr_len, uint32_t j, uint32_t n_ops) {
   const uint64_t base = v.in.resp_off[p];
   const uint8_t* b = v.in.wire + base;
   uint32_t off, len;
@@ -200,7 +201,7 @@ W1D_HD uint32_t op_level(const View& v, uint32_t p, uint32_t tr_off, uint32_t tr
 }
 
 // ---- level 4, per response: status, count, slices, and the slots nobody decoded ----
-W1D_HD void resp_final(const View& v, uint32_t p, uint32_t bits, const Level1& l, uint32_t n_ops) {
+WIRE_HD void resp_final(const View& v, uint32_t p, uint32_t bits, const Level1& l, uint32_t n_ops) {
   const mochi_result_decoded& out = v.out;
   const uint64_t base = v.in.resp_off[p];
   const bool bad = bits != 0, parsed = !bad && parsed_kind(v.in.resp_kind[p]);
@@ -216,7 +217,7 @@ W1D_HD void resp_final(const View& v, uint32_t p, uint32_t bits, const Level1& l
 }
 
 // ---- the coalesced TransactionResult per request (MochiDBClient.java:177-179 / :384-386) ----
-W1D_HD void coalesce_req(const mochi_result_tallied& t, const mochi_result_coalesced& o, uint32_t q) {
+WIRE_HD void coalesce_req(const mochi_result_tallied& t, const mochi_result_coalesced& o, uint32_t q) {
   const bool accept = (t.accept_bits[q >> 5] >> (q & 31)) & 1;
   const uint32_t k = t.n_ops[q], p0 = t.req_resp_off[q], np = t.req_resp_off[q + 1] - p0;
   for (uint32_t j = 0; j < k; j++) {

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void k_rr_resp(RRArgs a) {
   const uint8_t kind = in.resp_kind[p];
   uint32_t bits = 0;
   if (parsed_kind(kind)) bits = resp_level(in.wire + in.resp_off[p], in.resp_len[p], kind, o);
-  const uint32_t n_ops = in.n_ops[w1d::request_of(in.req_resp_off, in.n_reqs, p)];
+  const uint32_t n_ops = in.n_ops[wire::request_of(in.req_resp_off, in.n_reqs, p)];
   a.st_bits[p] = bits;
   ((uint4*)a.l1)[2 * p] = make_uint4(o.tr_off, o.tr_len, o.n_wire, n_ops);
   ((uint4*)a.l1)[2 * p + 1] = make_uint4(o.rid_off, o.rid_len, o.nonce_off, o.nonce_len);

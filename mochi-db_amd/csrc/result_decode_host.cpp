@@ -12,7 +12,7 @@ namespace {
 
 const char* check_input(const mochi_result_replies* in) {
   const uint32_t P = in->n_resps, Q = in->n_reqs;
-  if (P > mochi::w1d::kMaxResps) return "more than 2^24 responses";
+  if (P > mochi::wire::kMaxResps) return "more than 2^24 responses";
   for (uint32_t p = 0; p < P; p++) {
     if (in->resp_off[p] > in->wire_len || in->resp_len[p] > in->wire_len - in->resp_off[p])
       return "a response slice lies outside wire";

@@ -7,7 +7,7 @@
 // include/mochi_hip.h (mochi_result_answers / mochi_write2_answer_source).
 //
 // Everything under `namespace rae` is __host__ __device__.  The walk is built on
-// the field walk of w1_decode.h (next_fld) and reads a body through (base
+// the field walk of wire_walk.h (next_fld) and reads a body through (base
 // pointer, offsets below the body length) alone;
 // microbench/result_encode_check.cpp runs it under a sanitizer.
 //
@@ -21,31 +21,32 @@
 //   Write2ToServer = [0A WriteCertificate] [12 Transaction]
 //   Transaction    = { 0A Operation }     Operation = [08 action] [12 operand1] [1A operand2]
 #pragma once
-#include "w1_decode.h"
+#include "carve.h"
 #include "w2_encode.h"
+#include "wire_walk.h"
 
 namespace mochi {
 namespace rae {
 
-using w1d::Fld;
-using w1d::next_fld;
+using wire::Fld;
+using wire::next_fld;
 
 constexpr uint32_t kMaxOps = MOCHI_MAX_OPS_PER_CERT;
 constexpr uint64_t kNone = ~0ull;
 constexpr uint32_t kActionWrite = 2;  // OperationAction.WRITE (MochiProtocol.proto:20-24)
 
 // ---- sizes ---------------------------------------------------------------------
-W1D_HD bool body_kind(uint8_t kind) { return kind == MOCHI_RR_WRITE2_ANS || kind == MOCHI_RR_READ; }
+WIRE_HD bool body_kind(uint8_t kind) { return kind == MOCHI_RR_WRITE2_ANS || kind == MOCHI_RR_READ; }
 
 // one OperationResult's body, from its slot
-W1D_HD uint64_t op_body(const mochi_result_answers& a, uint64_t s) {
+WIRE_HD uint64_t op_body(const mochi_result_answers& a, uint64_t s) {
   const uint8_t st = a.op_status[s];
   return enc_ld_opt_size(a.op_result_len[s]) + (a.op_flags[s] & MOCHI_RAO_HAS_CERT ? enc_ld_size(a.op_cert_len[s]) : 0) +
-         (a.op_existed[s] ? 2 : 0) + (st ? 1 + enc_varint_size(st) : 0);
+         (a.op_existed[s] ? 2 : 0) + (st ? 1 + wire::varint_size(st) : 0);
 }
-W1D_HD uint32_t rid_len(const mochi_result_answers& a, uint32_t p) { return a.rid_off ? a.rid_len[p] : 0; }
+WIRE_HD uint32_t rid_len(const mochi_result_answers& a, uint32_t p) { return a.rid_off ? a.rid_len[p] : 0; }
 // a Write2 answer has no nonce
-W1D_HD uint32_t nonce_len(const mochi_result_answers& a, uint32_t p) {
+WIRE_HD uint32_t nonce_len(const mochi_result_answers& a, uint32_t p) {
   return a.nonce_off && a.resp_kind[p] == MOCHI_RR_READ ? a.nonce_len[p] : 0;
 }
 
@@ -56,7 +57,7 @@ struct Sized {
 };
 // Response p.  op_rel (may be null) receives, per slot, where the operation's tag
 // lies inside the TransactionResult body (meaningful only for an OK message: below 2^31).
-W1D_HD Sized size_resp(const mochi_result_answers& a, uint32_t p, uint32_t* op_rel) {
+WIRE_HD Sized size_resp(const mochi_result_answers& a, uint32_t p, uint32_t* op_rel) {
   Sized z{0, 0, MOCHI_ENC_OK};
   if (!body_kind(a.resp_kind[p])) return z;
   const uint32_t k = a.resp_n_ops[p];
@@ -86,7 +87,7 @@ struct W2Body {
   uint32_t cert_off, cert_len;  // last length-delimited field 1; absent: 0 / 0
   uint32_t tx_off, tx_len;      // last length-delimited field 2
 };
-W1D_HD bool w2_top(const uint8_t* p, uint32_t len, W2Body& o) {
+WIRE_HD bool w2_top(const uint8_t* p, uint32_t len, W2Body& o) {
   o.cert_off = o.cert_len = o.tx_off = o.tx_len = 0;
   uint32_t pos = 0;
   Fld f;
@@ -108,7 +109,7 @@ struct W2Op {
   uint32_t op2_off, op2_len;  // last length-delimited field 3; absent: the operation's own offset, 0
 };
 // The next Operation of the Transaction in [pos, end): 1, 0 at the end, -1 malformed.
-W1D_HD int w2_next_op(const uint8_t* p, uint32_t& pos, uint32_t end, W2Op& o) {
+WIRE_HD int w2_next_op(const uint8_t* p, uint32_t& pos, uint32_t end, W2Op& o) {
   Fld f;
   int rc;
   while ((rc = next_fld(p, pos, end, f)) > 0) {
@@ -139,7 +140,7 @@ struct PlanView {
   mochi_write2_answer_source s;
   mochi_write2_answer_planned o;
 };
-W1D_HD void slot_put(const mochi_write2_answer_planned& o, uint64_t s, uint8_t status, uint8_t existed, uint8_t flags,
+WIRE_HD void slot_put(const mochi_write2_answer_planned& o, uint64_t s, uint8_t status, uint8_t existed, uint8_t flags,
                      uint64_t r_off, uint32_t r_len, uint64_t c_off, uint32_t c_len) {
   o.op_status[s] = status;
   o.op_existed[s] = existed;
@@ -149,7 +150,7 @@ W1D_HD void slot_put(const mochi_write2_answer_planned& o, uint64_t s, uint8_t s
   o.op_cert_off[s] = c_off;
   o.op_cert_len[s] = c_len;
 }
-W1D_HD void plan_msg(const PlanView& v, uint32_t m) {
+WIRE_HD void plan_msg(const PlanView& v, uint32_t m) {
   const mochi_write2_batch& b = v.b;
   const mochi_write2_answer_source& s = v.s;
   const uint32_t o0 = b.op_flags_off[m], o1 = b.op_flags_off[m + 1];

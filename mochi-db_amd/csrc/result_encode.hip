@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_rae_hdr(mochi_result_answers a, const u
     if (len == 0) continue;
     const uint32_t tx = resp_tx[p];
     uint8_t* m0 = wire + msg_off[p];
-    const uint32_t tx_at = 1 + enc_varint_size(tx);
+    const uint32_t tx_at = 1 + wire::varint_size(tx);
     if (j == 0) {
       Put h(m0);
       h.byte(0x0A);

@@ -3,11 +3,13 @@
 // (w1_decode_host.cpp), and the parsing both share.  Semantics:
 // include/mochi_hip.h (mochi_write1_replies / mochi_write1_decoded).
 //
-// Everything under `namespace w1d` is __host__ __device__ and reads the body
-// through (base pointer, offsets below the body length) alone: the host form
-// and every kernel run the same walk over the same bytes, so they cannot
-// disagree, and a stand-alone host program (microbench/w1_decode_check.cpp)
-// checks under a sanitizer that no read leaves the slice.
+// Everything under `namespace w1d` is __host__ __device__, built on the pointer
+// walk of wire_walk.h, and reads the body through (base pointer, offsets below
+// the body length) alone: the host form and every kernel run the same walk
+// over the same bytes, so they cannot disagree, and a stand-alone host program
+// (microbench/w1_decode_check.cpp) checks under a sanitizer that no read
+// leaves the slice.  Only what is about Write1 replies (MultiGrant,
+// WriteCertificate, the reply's levels) lives here.
 //
 // Wire layout (MochiProtocol.proto:107-161 + MultiGrant.grantSignatures = 5),
 // parsed as protobuf-java 3.16.3 parses it -- the rules of w2_decode.hip:
@@ -28,296 +30,21 @@
 
 #include "../../include/mochi_hip.h"
 #include "carve.h"
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define W1D_NOINLINE __noinline__
-#else
-#define W1D_NOINLINE
-#endif
-#define W1D_HD __host__ __device__ inline
+#include "wire_walk.h"
 
 namespace mochi {
 namespace w1d {
 
+using namespace wire;
+
 constexpr uint32_t kMaxEntries = 64;   // grants / grantSignatures / currentCertificates wire entries per decoded response
-constexpr uint32_t kGroupDepth = 100;  // CodedInputStream's default recursion limit
-constexpr uint32_t kStMal = 1u, kStFb = 2u;
-constexpr uint32_t kBad = 0xFFFFFFFFu;
-constexpr uint32_t kMaxResps = 1u << 24;  // 65 level-2 entries each: every total stays below 2^32
-
-struct Fld {
-  uint32_t field, wt;
-  uint64_t v;
-  uint32_t off, len;  // wire type 2 payload
-};
-
-W1D_HD bool vint(const uint8_t* p, uint32_t& pos, uint32_t end, uint64_t& v) {
-  uint64_t x = 0;
-  for (int i = 0; i < 10; i++) {
-    if (pos >= end) return false;
-    const uint32_t c = p[pos++];
-    x |= (uint64_t)(c & 0x7F) << (7 * i);
-    if (!(c & 0x80)) {
-      v = x;
-      return true;
-    }
-  }
-  return false;
-}
-
-W1D_HD bool vlen(const uint8_t* p, uint32_t& pos, uint32_t end, uint32_t& len) {
-  uint64_t l;
-  if (!vint(p, pos, end, l)) return false;
-  const int32_t l32 = (int32_t)(uint32_t)l;  // readRawVarint32
-  if (l32 < 0 || (uint32_t)l32 > end - pos) return false;
-  len = (uint32_t)l32;
-  return true;
-}
-
-// Skip the unknown group opened by `field`; the position after it, or kBad.
-// Out of line on the device: its stack lives in scratch memory.
-__host__ __device__ W1D_NOINLINE inline uint32_t skip_group(const uint8_t* p, uint32_t pos, uint32_t end, uint32_t field) {
-  uint32_t stack[kGroupDepth];
-  uint32_t depth = 1;
-  stack[0] = field;
-  while (depth > 0) {
-    uint64_t t64;
-    if (!vint(p, pos, end, t64)) return kBad;
-    const uint32_t t = (uint32_t)t64, f = t >> 3, wt = t & 7;
-    if (f == 0) return kBad;
-    uint32_t l;
-    uint64_t v;
-    switch (wt) {
-      case 0:
-        if (!vint(p, pos, end, v)) return kBad;
-        break;
-      case 1:
-        if (end - pos < 8) return kBad;
-        pos += 8;
-        break;
-      case 2:
-        if (!vlen(p, pos, end, l)) return kBad;
-        pos += l;
-        break;
-      case 3:
-        if (depth >= kGroupDepth) return kBad;
-        stack[depth++] = f;
-        break;
-      case 4:
-        if (stack[depth - 1] != f) return kBad;
-        depth--;
-        break;
-      case 5:
-        if (end - pos < 4) return kBad;
-        pos += 4;
-        break;
-      default:
-        return kBad;
-    }
-  }
-  return pos;
-}
-
-// Next field in [pos, end): 1 field, 0 end, -1 malformed.
-W1D_HD int next_fld(const uint8_t* p, uint32_t& pos, uint32_t end, Fld& f) {
-  if (pos >= end) return 0;
-  uint64_t t64;
-  if (!vint(p, pos, end, t64)) return -1;
-  const uint32_t t = (uint32_t)t64;
-  f.field = t >> 3;
-  f.wt = t & 7;
-  f.off = f.len = 0;
-  f.v = 0;
-  if (f.field == 0) return -1;
-  switch (f.wt) {
-    case 0:
-      return vint(p, pos, end, f.v) ? 1 : -1;
-    case 1:
-      if (end - pos < 8) return -1;
-      pos += 8;
-      return 1;
-    case 2:
-      if (!vlen(p, pos, end, f.len)) return -1;
-      f.off = pos;
-      pos += f.len;
-      return 1;
-    case 3: {
-      const uint32_t np = skip_group(p, pos, end, f.field);
-      if (np == kBad) return -1;
-      pos = np;
-      return 1;
-    }
-    case 5:
-      if (end - pos < 4) return -1;
-      pos += 4;
-      return 1;
-    default:
-      return -1;  // END_GROUP at message level, wire types 6 and 7
-  }
-}
-
-// Utf8.isValidUtf8: no overlong forms, no surrogates, nothing above U+10FFFF
-W1D_HD bool valid_utf8(const uint8_t* p, uint32_t off, uint32_t n) {
-  uint32_t i = 0;
-  while (i < n) {
-    // ASCII runs (keys, ids, the 128-character hex transactionHash) a word per step
-    // once the position is 4-byte aligned: the word lies inside the string
-    if (i + 4 <= n && ((uintptr_t)(p + off + i) & 3) == 0) {
-      uint32_t w;
-      __builtin_memcpy(&w, __builtin_assume_aligned(p + off + i, 4), 4);
-      if ((w & 0x80808080u) == 0) {
-        i += 4;
-        continue;
-      }
-    }
-    const uint32_t c = p[off + i];
-    if (c < 0x80) {
-      i++;
-    } else if (c < 0xC2) {
-      return false;
-    } else if (c < 0xE0) {
-      if (i + 1 >= n || (p[off + i + 1] & 0xC0) != 0x80) return false;
-      i += 2;
-    } else if (c < 0xF0) {
-      if (i + 2 >= n) return false;
-      const uint32_t c1 = p[off + i + 1], c2 = p[off + i + 2];
-      if ((c1 & 0xC0) != 0x80 || (c2 & 0xC0) != 0x80) return false;
-      if (c == 0xE0 && c1 < 0xA0) return false;
-      if (c == 0xED && c1 >= 0xA0) return false;
-      i += 3;
-    } else if (c < 0xF5) {
-      if (i + 3 >= n) return false;
-      const uint32_t c1 = p[off + i + 1], c2 = p[off + i + 2], c3 = p[off + i + 3];
-      if ((c1 & 0xC0) != 0x80 || (c2 & 0xC0) != 0x80 || (c3 & 0xC0) != 0x80) return false;
-      if (c == 0xF0 && c1 < 0x90) return false;
-      if (c == 0xF4 && c1 >= 0x90) return false;
-      i += 4;
-    } else {
-      return false;
-    }
-  }
-  return true;
-}
-
-W1D_HD bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n) {
-  for (uint32_t i = 0; i < n; i++)
-    if (a[i] != b[i]) return false;
-  return true;
-}
-// FNV-1a over the bytes, then a finalizer (murmur3's) so that strings that differ in
-// their last byte alone spread over a table: the slot hash of the claim tables
-// (w1_request.hip's key table, envelope.hip's msgId table).  It decides no output.
-W1D_HD uint32_t bytes_hash(const uint8_t* k, uint32_t n) {
-  uint32_t h = 0x811C9DC5u;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-  for (uint32_t i = 0; i < n; i++) h = (h ^ k[i]) * 0x01000193u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-W1D_HD bool key_eq(const uint8_t* p, uint32_t a, uint32_t al, uint32_t b, uint32_t bl) {
-  return al == bl && (a == b || bytes_eq(p + a, p + b, al));
-}
-
-W1D_HD uint32_t varint_size(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) {
-    v >>= 7;
-    n++;
-  }
-  return n;
-}
-
-// The Grant at [off, off+len) (proto_dev.h's parse_grant_t with CANON): does it
-// parse, what does it hold, and are its bytes exactly Grant.toByteArray() of
-// what they parse to (fields 1..5 in order, each at most once, none at its
-// default, one-byte tags, minimal varints, no unknown fields, status an int32).
-struct Grant {
-  int64_t ts;
-  int32_t status;
-  uint32_t oid_off, oid_len;
-  bool canon;
-};
-W1D_HD bool parse_grant(const uint8_t* p, uint32_t off, uint32_t len, Grant& g) {
-  uint32_t pos = off, last = 0;
-  const uint32_t end = off + len;
-  g.ts = 0;
-  g.status = 0;
-  g.oid_off = g.oid_len = 0;
-  bool cn = true;
-  while (pos < end) {
-    const uint32_t p0 = pos;
-    uint64_t t64;
-    if (!vint(p, pos, end, t64)) return false;
-    const uint32_t tag = (uint32_t)t64, field = tag >> 3, wt = tag & 7;
-    if (field == 0) return false;
-    cn = cn && pos - p0 == 1 && field > last;
-    last = field;
-    if (tag == 10 || tag == 34) {
-      const uint32_t p1 = pos;
-      uint32_t l;
-      if (!vlen(p, pos, end, l) || !valid_utf8(p, pos, l)) return false;
-      cn = cn && l != 0 && pos - p1 == varint_size(l);
-      if (tag == 10) {
-        g.oid_off = pos;
-        g.oid_len = l;
-      }
-      pos += l;
-      continue;
-    }
-    if (tag == 16 || tag == 24 || tag == 40) {
-      const uint32_t p1 = pos;
-      uint64_t v;
-      if (!vint(p, pos, end, v)) return false;
-      if (tag == 16) g.ts = (int64_t)v;
-      if (tag == 40) g.status = (int32_t)(uint32_t)v;  // readEnum: the low 32 bits
-      // a 10-byte varint carries bit 63 alone in its last byte
-      cn = cn && v != 0 && pos - p1 == varint_size(v) && (pos - p1 < 10 || p[pos - 1] == 1) &&
-           (tag != 40 || (int64_t)v == (int64_t)(int32_t)(uint32_t)v);
-      continue;
-    }
-    cn = false;  // an unknown field, a known one with a foreign wire type, or a group
-    uint32_t l;
-    uint64_t v;
-    switch (wt) {
-      case 0:
-        if (!vint(p, pos, end, v)) return false;
-        break;
-      case 1:
-        if (end - pos < 8) return false;
-        pos += 8;
-        break;
-      case 2:
-        if (!vlen(p, pos, end, l)) return false;
-        pos += l;
-        break;
-      case 3:
-        pos = skip_group(p, pos, end, field);
-        if (pos == kBad) return false;
-        break;
-      case 5:
-        if (end - pos < 4) return false;
-        pos += 4;
-        break;
-      default:
-        return false;
-    }
-  }
-  g.canon = cn;
-  return true;
-}
 
 // map<string, V> entry: key and value as MapEntry reads them (last occurrence of each; default empty)
 struct Entry {
   uint32_t koff, klen, voff, vlen, nval;
 };
 // validates the framing and the key; kind 1: every value is a Grant that must parse
-W1D_HD bool read_entry(const uint8_t* p, uint32_t off, uint32_t len, int kind, bool check, Entry& e) {
+WIRE_HD bool read_entry(const uint8_t* p, uint32_t off, uint32_t len, int kind, bool check, Entry& e) {
   e.koff = e.klen = e.voff = e.vlen = e.nval = 0;
   uint32_t pos = off;
   const uint32_t end = off + len;
@@ -348,7 +75,7 @@ struct MGScan {
   bool twice;
   uint32_t sid_off, sid_len, cl_off, cl_len;
 };
-W1D_HD bool scan_multigrant(const uint8_t* p, uint32_t off, uint32_t len, MGScan& m) {
+WIRE_HD bool scan_multigrant(const uint8_t* p, uint32_t off, uint32_t len, MGScan& m) {
   m.nge = m.nse = 0;
   m.twice = false;
   m.sid_off = m.sid_len = m.cl_off = m.cl_len = 0;
@@ -380,8 +107,8 @@ W1D_HD bool scan_multigrant(const uint8_t* p, uint32_t off, uint32_t len, MGScan
   return rc == 0;
 }
 
-// a WriteCertificate, all the way down
-W1D_HD bool valid_writecert(const uint8_t* p, uint32_t off, uint32_t len) {
+// a WriteCertificate, all the way down (the result decoder validates OperationResult.currentCertificate with it too)
+WIRE_HD bool valid_writecert(const uint8_t* p, uint32_t off, uint32_t len) {
   uint32_t pos = off;
   const uint32_t end = off + len;
   Fld f;
@@ -404,7 +131,7 @@ W1D_HD bool valid_writecert(const uint8_t* p, uint32_t off, uint32_t len) {
 }
 
 // a whole reply body (the shapes level 1 declines are validated here by its lane)
-W1D_HD bool valid_reply(const uint8_t* p, uint32_t len) {
+WIRE_HD bool valid_reply(const uint8_t* p, uint32_t len) {
   uint32_t pos = 0;
   Fld f;
   int rc;
@@ -433,7 +160,7 @@ W1D_HD bool valid_reply(const uint8_t* p, uint32_t len) {
 // wire order; for each entry that is the first of its key, fn(index among the
 // distinct keys, that entry, the entry holding the key's final value).
 template <typename F>
-W1D_HD void for_map(const uint8_t* p, uint32_t off, uint32_t len, uint32_t field, F&& fn) {
+WIRE_HD void for_map(const uint8_t* p, uint32_t off, uint32_t len, uint32_t field, F&& fn) {
   uint32_t pos = off, idx = 0;
   const uint32_t end = off + len;
   Fld f;
@@ -468,7 +195,7 @@ struct Level1 {
   uint32_t n_keys;          // ... distinct keys among them
 };
 // Returns status bits.  With bits set nothing of `o` is to be used.
-W1D_HD uint32_t resp_level(const uint8_t* p, uint32_t len, Level1& o) {
+WIRE_HD uint32_t resp_level(const uint8_t* p, uint32_t len, Level1& o) {
   o.mg_off = o.mg_len = o.n_ce = o.n_keys = 0;
   uint32_t n_mg = 0, pos = 0;
   bool whole = false;
@@ -496,7 +223,7 @@ W1D_HD uint32_t resp_level(const uint8_t* p, uint32_t len, Level1& o) {
 }
 
 // value slice of the j-th currentCertificates entry on the wire (level 1 accepted the body)
-W1D_HD void cert_entry_value(const uint8_t* p, uint32_t len, uint32_t j, uint32_t& voff, uint32_t& vlen) {
+WIRE_HD void cert_entry_value(const uint8_t* p, uint32_t len, uint32_t j, uint32_t& voff, uint32_t& vlen) {
   uint32_t pos = 0, i = 0;
   Fld f;
   voff = vlen = 0;
@@ -517,7 +244,7 @@ struct Level2 {
   uint32_t ng;  // distinct grants
   uint32_t sid_off, sid_len, cl_off, cl_len;
 };
-W1D_HD uint32_t mg_level(const uint8_t* p, uint32_t off, uint32_t len, Level2& o) {
+WIRE_HD uint32_t mg_level(const uint8_t* p, uint32_t off, uint32_t len, Level2& o) {
   MGScan m;
   o.ng = o.sid_off = o.sid_len = o.cl_off = o.cl_len = 0;
   if (!scan_multigrant(p, off, len, m)) return kStMal;
@@ -540,14 +267,11 @@ W1D_HD uint32_t mg_level(const uint8_t* p, uint32_t off, uint32_t len, Level2& o
 }
 
 // index of the first table id equal to the serverId, 0xFFFF if none
-W1D_HD uint16_t find_server(const uint8_t* sid, uint32_t sl, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids) {
+WIRE_HD uint16_t find_server(const uint8_t* sid, uint32_t sl, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids) {
   for (uint32_t k = 0; k < n_ids && k < 0xFFFFu; k++)
     if (id_off[k + 1] - id_off[k] == sl && bytes_eq(ids + id_off[k], sid, sl)) return (uint16_t)k;
   return 0xFFFF;
 }
-
-// Grant.status as the classifier reads it: the value, or 0xFF for anything outside 0..254
-W1D_HD uint8_t status_u8(int32_t s) { return s >= 0 && s < 255 ? (uint8_t)s : (uint8_t)0xFF; }
 
 // What the decoder reads and writes: host pointers in the host form, device pointers in the kernels.
 struct View {
@@ -559,20 +283,9 @@ struct View {
   uint64_t* sig_src;  // [n_grants] wire offset of each signature, ~0 = none (device: scratch; host: null, copies at once)
 };
 
-// request of response p: req_resp_off is a CSR over the responses
-W1D_HD uint32_t request_of(const uint32_t* req_resp_off, uint32_t Q, uint32_t p) {
-  uint32_t lo = 0, hi = Q;  // the last q with req_resp_off[q] <= p
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (req_resp_off[mid] <= p) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // ---- emit, per decoded response: its grants and certificate entries -----------
 // g0 / c0: the response's first grant / certificate slot.
-W1D_HD void emit_resp(const View& v, uint32_t p, const uint32_t mg_off, const uint32_t mg_len, uint32_t g0, uint32_t c0) {
+WIRE_HD void emit_resp(const View& v, uint32_t p, const uint32_t mg_off, const uint32_t mg_len, uint32_t g0, uint32_t c0) {
   const mochi_write1_replies& in = v.in;
   const mochi_write1_decoded& out = v.out;
   const uint64_t base = in.resp_off[p];
@@ -631,7 +344,7 @@ W1D_HD void emit_resp(const View& v, uint32_t p, const uint32_t mg_off, const ui
 }
 
 // is a response of this kind parsed at all
-W1D_HD bool parsed_kind(uint8_t kind) { return kind == MOCHI_W1_OK || kind == MOCHI_W1_REFUSED; }
+WIRE_HD bool parsed_kind(uint8_t kind) { return kind == MOCHI_W1_OK || kind == MOCHI_W1_REFUSED; }
 
 }  // namespace w1d
 

@@ -22,7 +22,7 @@ constexpr uint32_t kW1WrongShard = 1;  // OperationResultStatus.WRONG_SHARD
 __host__ __device__ inline int64_t w1_ts(int64_t epoch, uint32_t seed) { return (int64_t)((uint64_t)epoch + seed); }
 // bytes of a new Grant (the key is never empty: an empty key FAILED)
 __host__ __device__ inline uint64_t w1_grant_size(uint32_t key_len, uint32_t hash_len, int64_t ts, bool wrong_shard) {
-  return enc_ld_size(key_len) + (wrong_shard || ts == 0 ? 0 : 1 + enc_varint_size((uint64_t)ts)) +
+  return enc_ld_size(key_len) + (wrong_shard || ts == 0 ? 0 : 1 + wire::varint_size((uint64_t)ts)) +
          enc_ld_opt_size(hash_len) + (wrong_shard ? 2 : 0);
 }
 // slots of the claim table: a power of two >= 2 * n_ops (load factor <= 1/2)

@@ -282,9 +282,9 @@ __global__ __launch_bounds__(256) void k_w1_emit(mochi_write1_batch b, mochi_wri
   const uint32_t kl = b.op_key_len[o], hl = b.req_hash_len[q];
   const uint64_t pos = len_off[o];
   uint8_t* const dst = out.grant_bytes + pos;
-  const uint32_t ts_bytes = ts ? 1 + enc_varint_size((uint64_t)ts) : 0;
-  const uintptr_t d_key = (uintptr_t)dst + 1 + enc_varint_size(kl);
-  const uintptr_t d_hash = d_key + kl + ts_bytes + 1 + enc_varint_size(hl);  // meaningful when hl != 0
+  const uint32_t ts_bytes = ts ? 1 + wire::varint_size((uint64_t)ts) : 0;
+  const uintptr_t d_key = (uintptr_t)dst + 1 + wire::varint_size(kl);
+  const uintptr_t d_hash = d_key + kl + ts_bytes + 1 + wire::varint_size(hl);  // meaningful when hl != 0
   if (l == 0) {
     Put p(dst);
     p.byte(0x0A);

@@ -6,28 +6,29 @@
 //
 // Everything under `namespace w1q` is __host__ __device__ and reads a body
 // through (base pointer, offsets below the body length) alone, with the field
-// walk of w1_decode.h (w1d::next_fld and friends): the host form and every
+// walk of wire_walk.h (wire::next_fld and friends): the host form and every
 // kernel run the same walk over the same bytes, and a stand-alone host program
 // (microbench/w1_request_check.cpp) checks under a sanitizer that no read
 // leaves the slice.
 //
 // Wire layout (MochiProtocol.proto:51-60, :92-97), parsed as protobuf-java
-// 3.16.3 parses it (the rules of w1_decode.h):
+// 3.16.3 parses it (the rules of wire_walk.h):
 //   Write1ToServer = [0A clientId] [12 Transaction] [18 seed] [22 transactionHash]
 //   Transaction    = { 0A Operation }
 //   Operation      = [08 action] [12 operand1] [1A operand2] [22 operand3]
 #pragma once
-#include "w1_decode.h"
+#include "carve.h"
 #include "w1_issue.h"
+#include "wire_walk.h"
 
 namespace mochi {
 namespace w1q {
 
-using w1d::Fld;
-using w1d::kStFb;
-using w1d::kStMal;
-using w1d::next_fld;
-using w1d::valid_utf8;
+using wire::Fld;
+using wire::kStFb;
+using wire::kStMal;
+using wire::next_fld;
+using wire::valid_utf8;
 
 constexpr uint32_t kMaxReqs = 1u << 24;  // 64 ops each: every total stays below 2^32
 constexpr uint32_t kMaxOps = MOCHI_MAX_OPS_PER_CERT;
@@ -40,7 +41,7 @@ constexpr uint8_t kHeld = MOCHI_W1OP_LOCAL | MOCHI_W1OP_HAS_SVOC;
 struct Op {
   uint32_t action, k_off, k_len;
 };
-W1D_HD bool op_level(const uint8_t* p, uint32_t off, uint32_t len, bool check, Op& o) {
+WIRE_HD bool op_level(const uint8_t* p, uint32_t off, uint32_t len, bool check, Op& o) {
   o.action = o.k_off = o.k_len = 0;
   uint32_t pos = off;
   const uint32_t end = off + len;
@@ -61,12 +62,12 @@ W1D_HD bool op_level(const uint8_t* p, uint32_t off, uint32_t len, bool check, O
 }
 
 // the wire half of mochi_write1_batch.op_flags
-W1D_HD uint8_t action_flags(uint32_t action) {
+WIRE_HD uint8_t action_flags(uint32_t action) {
   return action == 2 ? (uint8_t)MOCHI_W1OP_WRITE : action == 1 ? (uint8_t)MOCHI_W1OP_DELETE : (uint8_t)0;
 }
 
 // Framing of the Transaction at [off, off+len): its Operation entries counted; false = malformed.
-W1D_HD bool tx_count(const uint8_t* p, uint32_t off, uint32_t len, uint32_t& n_ent) {
+WIRE_HD bool tx_count(const uint8_t* p, uint32_t off, uint32_t len, uint32_t& n_ent) {
   uint32_t pos = off;
   const uint32_t end = off + len;
   Fld f;
@@ -78,7 +79,7 @@ W1D_HD bool tx_count(const uint8_t* p, uint32_t off, uint32_t len, uint32_t& n_e
 }
 
 // ... and every Operation of it, whole
-W1D_HD bool valid_tx(const uint8_t* p, uint32_t off, uint32_t len) {
+WIRE_HD bool valid_tx(const uint8_t* p, uint32_t off, uint32_t len) {
   uint32_t pos = off;
   const uint32_t end = off + len;
   Fld f;
@@ -91,7 +92,7 @@ W1D_HD bool valid_tx(const uint8_t* p, uint32_t off, uint32_t len) {
 }
 
 // slice of the j-th Operation entry of a Transaction whose framing tx_count accepted
-W1D_HD void tx_entry(const uint8_t* p, uint32_t off, uint32_t len, uint32_t j, uint32_t& eoff, uint32_t& elen) {
+WIRE_HD void tx_entry(const uint8_t* p, uint32_t off, uint32_t len, uint32_t j, uint32_t& eoff, uint32_t& elen) {
   uint32_t pos = off, i = 0;
   const uint32_t end = off + len;
   Fld f;
@@ -116,7 +117,7 @@ struct Level1 {
 // Returns status bits.  With bits set nothing of `o` is to be used.  A request
 // outside the level-by-level shape (a second transaction, more than kMaxOps
 // operations) is validated whole here: FALLBACK is never malformed.
-W1D_HD uint32_t req_level(const uint8_t* p, uint32_t len, Level1& o) {
+WIRE_HD uint32_t req_level(const uint8_t* p, uint32_t len, Level1& o) {
   o.tx_off = o.tx_len = o.n_ent = o.seed = o.cl_off = o.cl_len = o.h_off = o.h_len = 0;
   uint32_t pos = 0, n_tx = 0;
   Fld f;
@@ -158,7 +159,7 @@ struct View {
 };
 
 // the per-request outputs but req_op_off; returns the request's op count
-W1D_HD uint32_t final_req(const View& v, uint32_t q, uint32_t bits, const Level1& l) {
+WIRE_HD uint32_t final_req(const View& v, uint32_t q, uint32_t bits, const Level1& l) {
   const mochi_write1_requests_decoded& out = v.out;
   const bool ok = bits == 0;
   const uint64_t base = ok ? v.in.msg_off[q] : 0;
@@ -172,7 +173,7 @@ W1D_HD uint32_t final_req(const View& v, uint32_t q, uint32_t bits, const Level1
 }
 
 // op o = entry j of OK request q: key slice and wire flags
-W1D_HD void emit_op(const View& v, uint32_t q, uint32_t tx_off, uint32_t tx_len, uint32_t j, uint32_t o) {
+WIRE_HD void emit_op(const View& v, uint32_t q, uint32_t tx_off, uint32_t tx_len, uint32_t j, uint32_t o) {
   const uint64_t base = v.in.msg_off[q];
   const uint8_t* b = v.in.wire + base;
   uint32_t eo, el;
@@ -185,7 +186,7 @@ W1D_HD void emit_op(const View& v, uint32_t q, uint32_t tx_off, uint32_t tx_len,
 }
 
 // does the op take part in the key numbering
-W1D_HD bool has_key(uint8_t flags, uint32_t key_len) { return (flags & kWD) && key_len != 0; }
+WIRE_HD bool has_key(uint8_t flags, uint32_t key_len) { return (flags & kWD) && key_len != 0; }
 
 // the join, per op (host pointers or device pointers)
 struct JoinArgs {
@@ -199,7 +200,7 @@ struct JoinArgs {
   int64_t* op_epoch;
   uint32_t* op_stored;
 };
-W1D_HD void join_op(const JoinArgs& a, uint32_t o) {
+WIRE_HD void join_op(const JoinArgs& a, uint32_t o) {
   const uint32_t u = a.op_obj[o];
   uint8_t f = a.op_flags_wire[o];
   int64_t epoch = 0;
@@ -207,7 +208,7 @@ W1D_HD void join_op(const JoinArgs& a, uint32_t o) {
   if (u != MOCHI_W1_NONE) {
     f |= a.ks.key_flags[u] & kHeld;
     epoch = a.ks.key_epoch[u];
-    const int64_t ts = w1_ts(epoch, a.req_seed[w1d::request_of(a.req_op_off, a.n_reqs, o)]);
+    const int64_t ts = w1_ts(epoch, a.req_seed[wire::request_of(a.req_op_off, a.n_reqs, o)]);
     const uint32_t g1 = a.ks.key_given_off[u + 1];
     for (uint32_t g = a.ks.key_given_off[u]; g < g1; g++)
       if (a.ks.given_ts[g] == ts) {

@@ -112,10 +112,10 @@ __global__ __launch_bounds__(256) void k_w1q_emit(W1ReqArgs a) {
   emit_op(a.v, lo, l.x, l.y, o - (uint32_t)a.off64[lo], o);
 }
 
-// the slot a key's probe starts at (w1_decode.h bytes_hash: keys that differ in their
+// the slot a key's probe starts at (wire_walk.h bytes_hash: keys that differ in their
 // last byte alone spread over the table)
 __device__ __forceinline__ uint32_t key_slot(const uint8_t* __restrict__ k, uint32_t n, uint32_t mask) {
-  return w1d::bytes_hash(k, n) & mask;
+  return wire::bytes_hash(k, n) & mask;
 }
 
 __global__ __launch_bounds__(256) void k_w1q_claim(W1ReqArgs a) {
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_w1q_claim(W1ReqArgs a) {
       const uint32_t prev = atomicCAS(&a.tbl_op[h], kNone, o);
       // the claimer's slice was written by k_w1q_emit, a launch ago
       if (prev == kNone || prev == o ||
-          (out.op_key_len[prev] == kl && w1d::bytes_eq(a.v.in.wire + out.op_key_off[prev], k, kl))) {
+          (out.op_key_len[prev] == kl && wire::bytes_eq(a.v.in.wire + out.op_key_off[prev], k, kl))) {
         atomicMin(&a.tbl_min[h], o);
         slot = h;
         break;

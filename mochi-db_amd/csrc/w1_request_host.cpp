@@ -35,7 +35,7 @@ int write1_request_decode(const mochi_write1_requests* in, mochi_write1_requests
       uint32_t eo, el;
       Op op;
       tx_entry(b, l1[q].tx_off, l1[q].tx_len, j, eo, el);
-      if (!op_level(b, eo, el, true, op)) bits = mochi::w1d::kStMal;
+      if (!op_level(b, eo, el, true, op)) bits = mochi::wire::kStMal;
     }
     out->req_op_off[q] = n_ops;
     n_ops += final_req(v, q, bits, l1[q]);

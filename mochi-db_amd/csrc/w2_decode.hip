@@ -51,30 +51,8 @@ struct Fld {
   uint32_t off, len;  // wt 2 payload (message-relative)
 };
 
-__device__ __forceinline__ bool vint(ByteReader& r, uint32_t& pos, uint32_t end, uint64_t& v) {
-  uint64_t x = 0;
-#pragma unroll 1
-  for (int i = 0; i < 10; i++) {
-    if (pos >= end) return false;
-    const uint32_t c = r.at(pos++);
-    x |= (uint64_t)(c & 0x7F) << (7 * i);
-    if (!(c & 0x80)) {
-      v = x;
-      return true;
-    }
-  }
-  return false;
-}
-
-__device__ __forceinline__ bool vlen(ByteReader& r, uint32_t& pos, uint32_t end, uint32_t& len) {
-  uint64_t l;
-  if (!vint(r, pos, end, l)) return false;
-  const int32_t l32 = (int32_t)(uint32_t)l;  // readRawVarint32
-  if (l32 < 0 || (uint32_t)l32 > end - pos) return false;
-  len = (uint32_t)l32;
-  return true;
-}
-
+// vint / vlen over the ByteReader: proto_dev.h.
+//
 // Skip an unknown group opened by `field` (skipMessage + checkLastTagWas).
 // Rare: kept out of line so its stack does not weigh on the common path, and
 // called with plain values -- a reader or position passed by reference would

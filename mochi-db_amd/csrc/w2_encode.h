@@ -17,20 +17,13 @@
 #include <stdint.h>
 
 #include "../../include/mochi_hip.h"
+#include "wire_walk.h"
 
 namespace mochi {
 
-// bytes of the minimal varint encoding of v
-__host__ __device__ inline uint32_t enc_varint_size(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) {
-    v >>= 7;
-    n++;
-  }
-  return n;
-}
+// sizes on wire::varint_size, the bytes of a minimal varint (wire_walk.h):
 // tag (one byte: every field number here is below 16) + length varint + payload
-__host__ __device__ inline uint64_t enc_ld_size(uint64_t payload) { return 1 + enc_varint_size(payload) + payload; }
+__host__ __device__ inline uint64_t enc_ld_size(uint64_t payload) { return 1 + wire::varint_size(payload) + payload; }
 // the same, omitted when empty (proto3 default)
 __host__ __device__ inline uint64_t enc_ld_opt_size(uint64_t payload) { return payload ? enc_ld_size(payload) : 0; }
 // body of a grants-map entry: key objectId + value Grant
@@ -41,7 +34,7 @@ __host__ __device__ inline uint64_t enc_e1_body(uint32_t oid_len, uint32_t grant
 __host__ __device__ inline uint64_t enc_e5_body(uint32_t oid_len) { return enc_ld_size(oid_len) + 3 + MOCHI_RSA_BYTES; }
 // one Operation's body
 __host__ __device__ inline uint64_t enc_op_body(uint32_t action, uint32_t l1, uint32_t l2) {
-  return (action ? 1 + enc_varint_size(action) : 0) + enc_ld_opt_size(l1) + enc_ld_opt_size(l2);
+  return (action ? 1 + wire::varint_size(action) : 0) + enc_ld_opt_size(l1) + enc_ld_opt_size(l2);
 }
 constexpr uint64_t kEncMaxMsg = 0x7FFFFFFFull;  // a message of 2^31 bytes or more is MOCHI_ENC_TOO_LONG
 
@@ -91,11 +84,6 @@ hipError_t launch_w2_enc_emit(const W2EncArgs& a, hipStream_t stream);
 }  // namespace mochi
 
 namespace mochi_host {
-// The host twin of proto_dev.h's parse_grant, reduced to what the encoder
-// needs: does the Grant parse (protobuf-java 3.16.3 semantics, strict UTF-8 on
-// objectId and transactionHash, groups up to the recursion limit), and where is
-// its objectId (the last field 1 given).
-bool grant_object_id(const uint8_t* p, uint32_t len, uint32_t& oid_off, uint32_t& oid_len);
 // mochi_write2_encode without the argument checks of the C layer; `err` names
 // an inconsistent input (MOCHI_EINVAL).
 int write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids,

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_enc_hdr_mg(mochi_write2_source s, const
   const uint32_t sl = id_off[sg + 1] - id_off[sg];
   const uint64_t mg = mg_gpart[i] + enc_ld_opt_size(cl) + enc_ld_opt_size(sl);
   uint8_t* const base = wire + msg_off[m];
-  Put o(base + 1 + enc_varint_size(msg_wc[m]) + mg_rel[i]);
+  Put o(base + 1 + wire::varint_size(msg_wc[m]) + mg_rel[i]);
   o.byte(0x0A);
   o.varint(enc_ld_size(sl) + enc_ld_size(mg));
   o.ld(0x0A, sid, sl);

@@ -10,147 +10,6 @@
 #include "wire_put.h"
 
 namespace mochi_host {
-namespace {
-
-constexpr int kRecursionLimit = 100;  // CodedInputStream.DEFAULT_RECURSION_LIMIT (proto_dev.h kDeepGroupDepth)
-
-struct Rd {
-  const uint8_t* p;
-  uint32_t len, pos = 0;
-  bool varint(uint64_t& v) {
-    uint64_t x = 0;
-    for (int i = 0; i < 10; i++) {
-      if (pos >= len) return false;
-      const uint32_t c = p[pos++];
-      x |= (uint64_t)(c & 0x7F) << (7 * i);
-      if (!(c & 0x80)) {
-        v = x;
-        return true;
-      }
-    }
-    return false;
-  }
-};
-
-// Utf8.isValidUtf8 (proto_dev.h valid_utf8)
-bool valid_utf8(const uint8_t* s, uint32_t n) {
-  uint32_t i = 0;
-  while (i < n) {
-    const uint32_t c = s[i];
-    if (c < 0x80) {
-      i++;
-      continue;
-    }
-    if (c < 0xC2) return false;
-    if (c < 0xE0) {
-      if (i + 1 >= n || (s[i + 1] & 0xC0) != 0x80) return false;
-      i += 2;
-      continue;
-    }
-    if (c < 0xF0) {
-      if (i + 2 >= n) return false;
-      const uint32_t c1 = s[i + 1], c2 = s[i + 2];
-      if ((c1 & 0xC0) != 0x80 || (c2 & 0xC0) != 0x80) return false;
-      if (c == 0xE0 && c1 < 0xA0) return false;
-      if (c == 0xED && c1 >= 0xA0) return false;
-      i += 3;
-      continue;
-    }
-    if (c < 0xF5) {
-      if (i + 3 >= n) return false;
-      const uint32_t c1 = s[i + 1], c2 = s[i + 2], c3 = s[i + 3];
-      if ((c1 & 0xC0) != 0x80 || (c2 & 0xC0) != 0x80 || (c3 & 0xC0) != 0x80) return false;
-      if (c == 0xF0 && c1 < 0x90) return false;
-      if (c == 0xF4 && c1 >= 0x90) return false;
-      i += 4;
-      continue;
-    }
-    return false;
-  }
-  return true;
-}
-
-bool rd_string(Rd& r, uint32_t& off, uint32_t& len) {
-  uint64_t l;
-  if (!r.varint(l)) return false;
-  const int32_t l32 = (int32_t)(uint32_t)l;
-  if (l32 < 0 || (uint32_t)l32 > r.len - r.pos) return false;
-  if (!valid_utf8(r.p + r.pos, (uint32_t)l32)) return false;
-  off = r.pos;
-  len = (uint32_t)l32;
-  r.pos += (uint32_t)l32;
-  return true;
-}
-
-}  // namespace
-
-// proto_dev.h parse_grant_t<kDeepGroupDepth>, statement for statement
-bool grant_object_id(const uint8_t* p, uint32_t len, uint32_t& oid_off, uint32_t& oid_len) {
-  Rd r{p, len};
-  uint32_t ooff = 0, olen = 0, hoff, hlen;
-  uint32_t stack[kRecursionLimit];
-  int depth = 0;
-  while (r.pos < r.len) {
-    uint64_t tag64;
-    if (!r.varint(tag64)) return false;
-    const uint32_t tag = (uint32_t)tag64, field = tag >> 3, wt = tag & 7;
-    if (field == 0) return false;
-    if (depth > 0) {
-      if (wt == 4) {
-        if (stack[depth - 1] != field) return false;
-        depth--;
-        continue;
-      }
-    } else {
-      if (tag == 10) {
-        if (!rd_string(r, ooff, olen)) return false;
-        continue;
-      }
-      if (tag == 16 || tag == 24 || tag == 40) {
-        uint64_t v;
-        if (!r.varint(v)) return false;
-        continue;
-      }
-      if (tag == 34) {
-        if (!rd_string(r, hoff, hlen)) return false;
-        continue;
-      }
-    }
-    switch (wt) {
-      case 0: {
-        uint64_t v;
-        if (!r.varint(v)) return false;
-        break;
-      }
-      case 1:
-        if (r.len - r.pos < 8) return false;
-        r.pos += 8;
-        break;
-      case 2: {
-        uint64_t l;
-        if (!r.varint(l)) return false;
-        const int32_t l32 = (int32_t)(uint32_t)l;
-        if (l32 < 0 || (uint32_t)l32 > r.len - r.pos) return false;
-        r.pos += (uint32_t)l32;
-        break;
-      }
-      case 3:
-        if (depth >= kRecursionLimit) return false;
-        stack[depth++] = field;
-        break;
-      case 5:
-        if (r.len - r.pos < 4) return false;
-        r.pos += 4;
-        break;
-      default:  // 4 (END_GROUP at top level), 6, 7
-        return false;
-    }
-  }
-  if (depth != 0) return false;
-  oid_off = ooff;
-  oid_len = olen;
-  return true;
-}
 
 int write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32_t* id_off, uint32_t n_ids,
                   uint8_t* wire, uint64_t wire_cap, uint64_t* msg_off, uint32_t* msg_len, uint8_t* status,
@@ -187,12 +46,15 @@ int write2_encode(const mochi_write2_source* s, const uint8_t* ids, const uint32
     for (uint32_t g = s->mg_grant_off[i]; g < s->mg_grant_off[i + 1]; g++) {
       const uint64_t go = s->grant_off[g];
       const uint32_t gl = s->grant_len[g];
-      uint32_t oo = 0, ol = 0;
-      if (!inside(go, gl, s->grant_bytes_len) || !grant_object_id(s->grant_bytes + go, gl, oo, ol)) {
+      // does the Grant parse, and where is its objectId (the last field 1 given): the
+      // pointer walk's parser, which decides as proto_dev.h's does in w2_encode.hip
+      wire::Grant gr;
+      if (!inside(go, gl, s->grant_bytes_len) || !wire::parse_grant(s->grant_bytes + go, 0, gl, gr)) {
         mg_bad[i] = 1;
         continue;
       }
-      g_oid[2 * (size_t)g] = oo;
+      const uint32_t ol = gr.oid_len;
+      g_oid[2 * (size_t)g] = gr.oid_off;
       g_oid[2 * (size_t)g + 1] = ol;
       part += enc_ld_size(enc_e1_body(ol, gl));
       if (s->sig) part += enc_ld_size(enc_e5_body(ol));

@@ -311,7 +311,7 @@ def parse_protobuf(body: bytes, kind: int):
 # there, and why the decoder's verdict stands.  crosscheck() requires exactly this difference;
 # tests/test_result_reply_cpu.py has one test per entry.
 PYTHON_DEPARTS = {
-    # the decoder's rule is the one of csrc/w1_decode.h: groups to depth 100, counted alone, wherever
+    # the decoder's rule is the one of csrc/wire_walk.h: groups to depth 100, counted alone, wherever
     # the message sits.  upb (as protobuf-java's recursion limit) also counts the messages around the
     # group: the two around an OperationResult's fields, so it refuses 99 and 100 groups there (at the top
     # level, with no message around them, it draws the line where the decoder does)

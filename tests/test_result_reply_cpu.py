@@ -44,7 +44,7 @@ def _case(name):
 @pytest.mark.parametrize("name", sorted(M.PYTHON_DEPARTS))
 def test_where_python_departs(name):
     """Each named departure, alone: the runtime's verdict, the model's, and the host form's
-    (which is the model's: the rule of protobuf-java as csrc/w1_decode.h states it)."""
+    (which is the model's: the rule of protobuf-java as csrc/wire_walk.h states it)."""
     pytest.importorskip("google.protobuf")
     c = _case(name)
     rule = M.PYTHON_DEPARTS[name][0]

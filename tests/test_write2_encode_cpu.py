@@ -154,6 +154,32 @@ def test_bad_messages_are_emitted_empty_and_neighbours_unchanged():
     assert mh.write2_encode_bound(src, max(len(x) for x in C.IDS)) >= wire.size
 
 
+def test_grant_mutants_against_the_oracle():
+    """One message per mutant of the grant corpus: BAD_GRANT exactly where the oracle's Grant
+    parser refuses the bytes, and otherwise the Python encoder's message keyed by the
+    objectId the oracle read."""
+    grants = C.grant_mutants()
+    src = C.mutant_source()
+    assert src.n_msgs == len(grants) > 3000
+    wire, off, ln, st = mh.encode_write2(src, C.IDS)
+    parsed = [O.grant_parse(gb) for gb in grants]
+    np.testing.assert_array_equal(st, [mh.ENC_BAD_GRANT if p is None else mh.ENC_OK for p in parsed])
+    assert 1000 < sum(p is not None for p in parsed) < len(grants) - 1000
+    op = W.encode_operation(2, "k", "v")
+    pos = 0
+    for m, (gb, p) in enumerate(zip(grants, parsed)):
+        assert int(off[m]) == pos
+        if p is None:
+            assert ln[m] == 0
+            continue
+        oid = p["object_id"].decode()
+        mg = W.encode_multigrant([(oid, gb)], C.IDS[0], "", "", [(oid, src.sig[m].tobytes())])
+        want = W.encode_write2([(C.IDS[0], mg)], [op])
+        assert wire[pos:pos + int(ln[m])].tobytes() == want, m
+        pos += int(ln[m])
+    assert pos == wire.size
+
+
 def test_inconsistent_source_is_refused():
     src = C.hand_source()
     src.cert_mg_off = src.cert_mg_off.copy()

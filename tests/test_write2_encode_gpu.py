@@ -45,9 +45,11 @@ def _stream():
 
 # 1. device == host ----------------------------------------------------------
 # align1023 / align1024: the single-block scan and the hipcub scan (the decoder's small-batch line)
+# mutants / mutants1023: the grant mutation corpus on both paths.  The host form parses with wire_walk.h, the device
+# form with proto_dev.h: the two Grant parsers against each other, group depths 16, 17, 100 and 101 included
 @pytest.mark.parametrize("name", ["r4", "r7k2", "client", "nosig", "hand", "hand_nosig", "steps", "steps_nosig",
                                   "wc16383", "wc16384", "msg16383", "msg16384", "bad", "align1023", "align1024",
-                                  "one", "none"])
+                                  "one", "none", "mutants", "mutants1023"])
 def test_device_form_equals_host_form(ver7, sources, name):
     import torch
 

@@ -260,6 +260,38 @@ def bad_source():
     return source(msgs), [0, mh.ENC_BAD_GRANT, 0, mh.ENC_BAD_SIGNER, 0, mh.ENC_BAD_GRANT, 0]
 
 
+def _groups(depth):
+    """An unknown group (field 9) nested `depth` deep."""
+    return b"\x4b" * depth + b"\x4c" * depth
+
+
+@functools.lru_cache(maxsize=None)
+def grant_mutants():
+    """The grant mutation corpus: every truncation and every single-bit flip of three
+    grants -- the demo grant; one with multi-byte UTF-8, all five fields, fixed32 /
+    fixed64 unknowns and a second objectId; one with unknown groups nested 1, 15, 16 and
+    17 deep (the device parser's register stack holds 16) -- and, unmutated, groups
+    nested 99, 100 and 101 deep (the recursion limit is 100)."""
+    grants = [
+        W.encode_grant("DEMO_KEY_1", 1342, "a" * 128),
+        W.encode_grant("kéy-€-\U0001f511", 1700000000000, "häsh" + "b" * 27, configstamp=7, status=1) +
+        b"\x4d\x01\x02\x03\x04" + b"\x49\x01\x02\x03\x04\x05\x06\x07\x08" + W._ld(1, b"second"),
+        W._ld(1, b"grp") + _groups(1) + _groups(15) + _groups(16) + _groups(17) + b"\x10\x05",
+    ]
+    out = []
+    for b in grants:
+        out += [b[:n] for n in range(len(b) + 1)]
+        out += [b[:i] + bytes([b[i] ^ (1 << bit)]) + b[i + 1:] for i in range(len(b)) for bit in range(8)]
+    out += [W._ld(1, b"deep") + _groups(d) for d in (99, 100, 101)]
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def mutant_source():
+    """One message per grant mutant: one MultiGrant of that one grant, signer 0, one operation."""
+    return source([([(0, [gb])], [(2, b"k", b"v")]) for gb in grant_mutants()])
+
+
 def byte_exact_sources():
     """name -> source, for the cases the host form must match workload.py byte for byte."""
     s4, s7 = synth(4, 1), synth(7, 2)
@@ -277,5 +309,6 @@ def device_sources():
     """Every source the device form is compared with the host form on."""
     d = dict(byte_exact_sources())
     a = align_source()
-    d.update(bad=bad_source()[0], align1024=a, align1023=head(a, 1023), one=head(a, 1), none=head(a, 0))
+    d.update(bad=bad_source()[0], align1024=a, align1023=head(a, 1023), one=head(a, 1), none=head(a, 0),
+             mutants=mutant_source(), mutants1023=head(mutant_source(), 1023))
     return d

@@ -220,7 +220,7 @@ PYTHON_DEPARTS = {
     # readTag throws invalidTag() for field number 0 wherever it reads a tag, inside an unknown group
     # too (UnknownFieldSet.Builder.mergeFrom); upb lets it pass there
     "flip:1:20:3": ("python_accepts", "field number 0 inside an unknown group: protobuf-java throws"),
-    # the decoder's rule is the one of csrc/w1_decode.h: groups to depth 100, counted alone.  upb (as
+    # the decoder's rule is the one of csrc/wire_walk.h: groups to depth 100, counted alone.  upb (as
     # protobuf-java's recursion limit) also counts the two messages around an Operation's fields, so it
     # refuses 99 and 100 groups there; the decoder skips them (they carry no value it reads)
     "group:op_100": ("python_rejects", "group depth is counted without the enclosing messages"),
