@@ -1319,7 +1319,9 @@ int mochi_result_coalesce_device(const mochi_result_tallied* tallied, mochi_resu
  * the per-slot arrays, which are n_slots long; slot_off need not be dense or
  * ascending and the slot runs of two responses must not overlap (as in the
  * decoder).  rid and nonce are slices of `ids`; either pair of arrays may be
- * NULL (empty); a Write2 answer has no nonce.  Per slot: op_status 0..254 is
+ * NULL (empty); a Write2 answer has no nonce.  `ids` may be the same pointer as
+ * `wire` (a read's nonce is a slice of the request it came in: see
+ * mochi_read_answer_plan); the encoder only reads both.  Per slot: op_status 0..254 is
  * written as a varint (128..254 take two bytes), 0xFF -- the decoder's
  * "absent" mark -- makes the response MOCHI_ENC_BAD_OP; op_existed;
  * op_flags = MOCHI_RAO_*; the `result` string and the certificate as slices of
@@ -1458,6 +1460,168 @@ int mochi_write2_answer_plan(const mochi_write2_batch* batch, const mochi_write2
  * are trusted, the bytes of `wire` are not. */
 int mochi_write2_answer_plan_device(const mochi_write2_batch* batch, const mochi_write2_answer_source* src,
                                     mochi_write2_answer_planned* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Read REQUEST DECODE: the server's side of a read.  The ReadToServer bodies a
+ * server received (field 105 of a ProtocolMessage, MochiProtocol.proto:72-76)
+ * become SoA arrays, with the parsing semantics of mochi_write1_request_decode
+ * (protobuf-java 3.16.3: singular fields last-wins, unknown fields and known
+ * field numbers with a foreign wire type skipped -- field 3 as a varint and
+ * field 4 of any type are unknown here --, groups to depth 100, field number 0
+ * or a bad varint malformed; clientId, nonce and operand1 / 2 / 3 of every
+ * Operation strict UTF-8; Operation.action the low 32 bits of its varint).  The
+ * bytes are a Byzantine client's: every read stays inside the request's slice.
+ *
+ *   ReadToServer = [0A clientId] [12 Transaction] [1A nonce]
+ *   Transaction  = { 0A Operation }
+ *   Operation    = [08 action] [12 operand1] [1A operand2] [22 operand3]
+ *
+ * Input: as mochi_write1_requests (n_reqs at most 2^24; slices may alias and
+ * have any alignment).
+ * ------------------------------------------------------------------------ */
+typedef mochi_write1_requests mochi_read_requests;
+
+/* Per-request decode status: the values and meanings of mochi_w1q_status. */
+enum mochi_rdq_status {
+  MOCHI_RDQ_OK = 0,
+  MOCHI_RDQ_MALFORMED = 1, /* protobuf-java would throw while parsing the body as a ReadToServer */
+  /* well-formed (validated whole, never malformed) but not decoded: `transaction`
+   * given more than once; more than MOCHI_MAX_OPS_PER_CERT operations */
+  MOCHI_RDQ_FALLBACK = 2,
+};
+#define MOCHI_RDOP_READ 0x01 /* op_flags: the action is READ (0, an absent action included) */
+
+/* Output; every array is the caller's.  Offsets point into `wire`; a field that
+ * is absent gives the request's own offset and length 0.  A request whose
+ * status is not OK has no ops and slices 0 / 0.
+ *   req_client_*: clientId.  req_nonce_*: nonce (with ids = wire they are the
+ *   nonce_off / nonce_len of mochi_result_answers).  req_op_off [Q+1]: a CSR.
+ * Per op, in transaction order: op_key_off / op_key_len = operand1; op_flags =
+ * MOCHI_RDOP_READ for action 0 and 0 for any other value; op_obj = the index
+ * of the op's key among the batch's distinct keys, MOCHI_W1_NONE for an op that
+ * has none.  Only READ ops with a non-empty operand1 take part (every op here
+ * belongs to an OK request); keys are compared byte for byte and numbered by
+ * their first op in op order, so the host and device forms give identical
+ * arrays.  key_op[u] = the first op that holds key u.
+ * Capacity: n_ops / n_keys / op_cap as in mochi_write1_requests_decoded: n_ops
+ * is always written; when op_cap < n_ops the call returns MOCHI_EINVAL and
+ * touches no per-op array, key_op or n_keys. */
+typedef struct mochi_read_requests_decoded {
+  uint8_t*  req_status;       /* [Q] enum mochi_rdq_status */
+  uint64_t* req_client_off;   /* [Q] */
+  uint32_t* req_client_len;   /* [Q] */
+  uint64_t* req_nonce_off;    /* [Q] */
+  uint32_t* req_nonce_len;    /* [Q] */
+  uint32_t* req_op_off;       /* [Q+1] */
+  uint32_t  n_ops;            /* out */
+  uint32_t  n_keys;           /* out (host form; the device form leaves it 0) */
+  uint32_t  op_cap, _pad0;    /* in  */
+  uint64_t* op_key_off;       /* [O] */
+  uint32_t* op_key_len;       /* [O] */
+  uint8_t*  op_flags;         /* [O] MOCHI_RDOP_* */
+  uint32_t* op_obj;           /* [O] */
+  uint32_t* key_op;           /* [op_cap]; n_keys entries written */
+} mochi_read_requests_decoded;
+
+/* A safe op_cap, as mochi_write1_request_decode_bound. */
+uint64_t mochi_read_request_decode_bound(uint64_t wire_len, uint32_t n_reqs);
+
+/* Host form: every array in host memory, no context, no GPU.  MOCHI_EINVAL for
+ * a request slice outside `wire` or more than 2^24 requests. */
+int mochi_read_request_decode(const mochi_read_requests* requests, mochi_read_requests_decoded* out);
+
+/* Device form: every array of `requests` and `out` and n_keys_dev (one
+ * uint32_t) in DEVICE memory, the structs themselves on the host.  A read signs
+ * nothing: the call hangs off the context (the answer encoder's owner).  Its
+ * scratch is the context's, apart from the other calls'; it takes the context's
+ * lock and orders itself behind the context's last call on another stream.  It
+ * waits once, for n_ops, applies the capacity rule on the host and returns with
+ * the remaining kernels enqueued on `stream` (hipStream_t; NULL = null stream);
+ * the number of distinct keys goes to *n_keys_dev.  The caller's offsets are
+ * trusted, the bytes of `wire` are not. */
+int mochi_read_request_decode_device(mochi_ctx* ctx, const mochi_read_requests* requests,
+                                     mochi_read_requests_decoded* out, uint32_t* n_keys_dev, void* stream);
+/* Per-kernel device time (ms) of the last mochi_read_request_decode_device call
+ * made while profiling was on (mochi_ctx_set_profiling) and that emitted: [0]
+ * k_rdq_req, [1] the entry scan, [2] k_w1q_ops, [3] k_rdq_final + the op scan +
+ * k_rdq_offsets, [4] k_rdq_emit, [5] the table clear + k_w1q_claim, [6]
+ * k_w1q_rank, [7] the key scan, [8] k_w1q_number.  Waits for that call.  n <= 9. */
+int mochi_ctx_read_read_decode_profile(mochi_ctx* ctx, float* kernel_ms, uint32_t n);
+
+/* ------------------------------------------------------------------------
+ * Read answer PLAN: decoded read requests and the store's state per distinct
+ * key to the encoder's input (InMemoryDataStore.processReadRequest :201-231 and
+ * processRead :75-103 over arrays).  The host looks the store up once per
+ * distinct key (key_op names an op that holds it) and gives, per key u,
+ * key_flags and the value and the certificate as slices of a `store` blob (a
+ * null value and an empty value both give length 0).
+ *
+ * Per request q:
+ *   MOCHI_RDA_NO_REPLY  the reference threw: req_status MALFORMED; an op
+ *     without MOCHI_RDOP_READ (checkAndFailOnReadOnly :217); an op with an empty
+ *     operand1 (:77); an op whose key is LOCAL but not PRESENT (:99 dereferences
+ *     null); an op whose key is LOCAL and PRESENT without HAS_CERT (:100,
+ *     setCurrentCertificate(null) throws).  resp_kind = MOCHI_RR_OTHER,
+ *     resp_n_ops = 0, every slot of the request absent (op_status 0xFF, the rest
+ *     0, as mochi_write2_answer_plan writes them).
+ *   MOCHI_RDA_HOST      req_status FALLBACK: resp_kind = MOCHI_RR_OTHER; the
+ *     caller builds this answer.
+ *   MOCHI_RDA_REPLY     everything else: resp_kind = MOCHI_RR_READ, resp_n_ops =
+ *     the op count (zero ops: an empty TransactionResult).  Per op: key not
+ *     LOCAL -> status 1 (WRONG_SHARD) alone; otherwise status 0, result = the
+ *     value slice with MOCHI_RAO_RESULT_STORE, existed = AVAILABLE,
+ *     MOCHI_RAO_HAS_CERT | MOCHI_RAO_CERT_STORE with the certificate slice (an
+ *     empty one is still written, as 12 00).  Every other field of a slot is 0.
+ * slot_off[q] = req_op_off[q]: the per-slot outputs are n_ops long and are the
+ * seven per-slot arrays of mochi_result_answers (n_slots = n_ops, wire = the
+ * requests' wire, store = the store blob).  The nonce goes to the encoder as
+ * nonce_off / nonce_len = req_nonce_off / req_nonce_len with ids = wire: `ids`
+ * may be the same pointer as `wire`.  A server that wants non-empty rids places
+ * them in the same allocation behind wire_len and passes an ids_len that covers
+ * them.
+ * ------------------------------------------------------------------------ */
+#define MOCHI_RDA_REPLY 0
+#define MOCHI_RDA_NO_REPLY 1
+#define MOCHI_RDA_HOST 2
+#define MOCHI_RDK_LOCAL 0x01     /* objectBelongsToCurrentShardServer (the CONFIG_KEY_PREFIX rule is the caller's) */
+#define MOCHI_RDK_PRESENT 0x02   /* a container exists */
+#define MOCHI_RDK_AVAILABLE 0x04 /* isValueAvailble() */
+#define MOCHI_RDK_HAS_CERT 0x08  /* getCurrentC() != null */
+typedef struct mochi_read_key_state {
+  uint32_t n_keys, _pad0;        /* U */
+  const uint8_t*  key_flags;     /* [U] MOCHI_RDK_* */
+  const uint64_t* key_value_off; /* [U] into the store blob */
+  const uint32_t* key_value_len;
+  const uint64_t* key_cert_off;  /* [U] into the store blob */
+  const uint32_t* key_cert_len;
+  uint64_t store_len;            /* size of the store blob (the host form checks slices against it) */
+} mochi_read_key_state;
+typedef struct mochi_read_answer_planned {
+  uint8_t*  plan_status;     /* [Q] MOCHI_RDA_* */
+  uint8_t*  resp_kind;       /* [Q] */
+  uint32_t* resp_n_ops;      /* [Q] */
+  uint64_t* slot_off;        /* [Q] = req_op_off[q] */
+  uint8_t*  op_status;       /* [O] */
+  uint8_t*  op_existed;
+  uint8_t*  op_flags;
+  uint64_t* op_result_off;
+  uint32_t* op_result_len;
+  uint64_t* op_cert_off;
+  uint32_t* op_cert_len;
+} mochi_read_answer_planned;
+/* Host form.  Of `decoded` it reads req_status, req_op_off, n_ops, op_key_len,
+ * op_flags and op_obj.  MOCHI_EINVAL for a NULL array, a req_op_off that is not
+ * a CSR over n_ops, an op_obj >= n_keys that is not MOCHI_W1_NONE, or a key
+ * slice outside store_len.  With n_reqs == 0 no pointer is needed. */
+int mochi_read_answer_plan(uint32_t n_reqs, const mochi_read_requests_decoded* decoded,
+                           const mochi_read_key_state* keys, mochi_read_answer_planned* out);
+/* Device form: every array in DEVICE memory (decoded->n_ops is the host field
+ * the decoder set); one kernel (k_rda_plan, lane = request) on `stream` on the
+ * current device, no host wait, no scratch: it may be enqueued right behind
+ * mochi_read_request_decode_device, and mochi_result_reply_encode_device right
+ * behind it.  The caller's own arrays are trusted. */
+int mochi_read_answer_plan_device(uint32_t n_reqs, const mochi_read_requests_decoded* decoded,
+                                  const mochi_read_key_state* keys, mochi_read_answer_planned* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * The ProtocolMessage ENVELOPE (MochiProtocol.proto:194-213, one frame of

@@ -16,6 +16,7 @@
 #include "ctx.h"
 #include "envelope.h"
 #include "mont.h"
+#include "read_request.h"
 #include "result_decode.h"
 #include "result_encode.h"
 #include "w1_decode.h"
@@ -1674,11 +1675,12 @@ int run_write1_request_device(mochi_signer* s, const mochi_write1_requests* r, m
   o->n_ops = a.n_ops = (uint32_t)tot;
   const bool fits = o->n_ops <= o->op_cap;
   if (fits) {
-    a.slots = (uint32_t)mochi::w1_table_slots(a.n_ops);
+    a.k.n_ops = a.n_ops;
+    a.k.slots = (uint32_t)mochi::w1_table_slots(a.n_ops);
     size_t scan_bytes = 0;
     HIP_TRY(mochi::enc_scan_temp_bytes(a.n_ops + 1, &scan_bytes));
-    if ((rc = s->w1q_tab.ensure(mochi::w1q_table_layout(a, nullptr))) || (rc = x.scan.ensure(scan_bytes))) return rc;
-    mochi::w1q_table_layout(a, s->w1q_tab.p);
+    if ((rc = s->w1q_tab.ensure(mochi::key_table_layout(a.k, nullptr))) || (rc = x.scan.ensure(scan_bytes))) return rc;
+    mochi::key_table_layout(a.k, s->w1q_tab.p);
     a.scan_temp = x.scan.p;
     a.scan_temp_bytes = x.scan.cap;
     HIP_TRY(mochi::launch_w1q_emit(a, st));
@@ -2003,6 +2005,136 @@ int mochi_write2_answer_plan_device(const mochi_write2_batch* b, const mochi_wri
   if (rc || !b->n_msgs) return rc;
   const mochi::rae::PlanView v{*b, *s, *o};
   HIP_TRY(mochi::launch_w2a_plan(v, (hipStream_t)stream));
+  return MOCHI_OK;
+}
+
+}  // extern "C"
+
+// ---- read request decoder and read answer plan (read_request.hip / read_request_host.cpp) ----
+namespace {
+
+int check_read_requests(const mochi_read_requests* r, const mochi_read_requests_decoded* o) {
+  if (!r || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (!o->req_op_off) return fail(MOCHI_EINVAL, "req_op_off required");
+  if (r->n_reqs && (!r->msg_off || !r->msg_len || (!r->wire && r->wire_len)))
+    return fail(MOCHI_EINVAL, "wire / msg_off / msg_len required");
+  if (r->n_reqs && (!o->req_status || !o->req_client_off || !o->req_client_len || !o->req_nonce_off || !o->req_nonce_len))
+    return fail(MOCHI_EINVAL, "the per-request outputs are required");
+  if (r->n_reqs > mochi::rdq::kMaxReqs) return fail(MOCHI_EINVAL, "more than 2^24 requests");
+  if (o->op_cap && (!o->op_key_off || !o->op_key_len || !o->op_flags || !o->op_obj || !o->key_op))
+    return fail(MOCHI_EINVAL, "the per-op outputs and key_op are required (op_cap > 0)");
+  return MOCHI_OK;
+}
+
+int rdq_capacity_error(const mochi_read_requests_decoded* o) {
+  return capacity_error("op_cap", o->op_cap, "decoded ops", o->n_ops);
+}
+
+int run_read_request_device(mochi_ctx* c, const mochi_read_requests* r, mochi_read_requests_decoded* o,
+                            uint32_t* n_keys_dev, hipStream_t st) {
+  const uint32_t Q = r->n_reqs;
+  EncState& x = c->rdq;
+  o->n_ops = o->n_keys = 0;
+  mochi::RdReqArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.in = *r;
+  a.v.out = *o;
+  a.Q = Q;
+  a.n_keys = n_keys_dev;
+  int rc = x.begin(a, mochi::rdq_layout, Q + 1, 8, c->profiling, mochi::kRdReqEvents);
+  if (rc) return rc;
+  // the context's scratch: a call on another stream waits for the last call's kernels
+  HIP_TRY(c->order.acquire(st));
+  HIP_TRY(mochi::launch_rdq_count(a, st));
+  if ((rc = x.fetch_totals(a.off64 + Q, 8, c->ev_tot, st))) return rc;
+  o->n_ops = a.n_ops = (uint32_t)*(const uint64_t*)x.tot.p;
+  const bool fits = o->n_ops <= o->op_cap;
+  if (fits) {
+    a.k.n_ops = a.n_ops;
+    a.k.slots = (uint32_t)mochi::w1_table_slots(a.n_ops);
+    size_t scan_bytes = 0;
+    HIP_TRY(mochi::enc_scan_temp_bytes(a.n_ops + 1, &scan_bytes));
+    if ((rc = c->rdq_tab.ensure(mochi::key_table_layout(a.k, nullptr))) || (rc = x.scan.ensure(scan_bytes))) return rc;
+    mochi::key_table_layout(a.k, c->rdq_tab.p);
+    a.scan_temp = x.scan.p;
+    a.scan_temp_bytes = x.scan.cap;
+    HIP_TRY(mochi::launch_rdq_emit(a, st));
+  }
+  x.ev_valid = a.ev && fits;
+  HIP_TRY(c->order.release(st));
+  return fits ? MOCHI_OK : rdq_capacity_error(o);
+}
+
+int check_read_plan(uint32_t n_reqs, const mochi_read_requests_decoded* d, const mochi_read_key_state* k,
+                    const mochi_read_answer_planned* o) {
+  if (!n_reqs) return MOCHI_OK;
+  if (!d || !k || !o) return fail(MOCHI_EINVAL, "null argument");
+  if (!d->req_status || !d->req_op_off) return fail(MOCHI_EINVAL, "req_status / req_op_off required");
+  if (d->n_ops && (!d->op_key_len || !d->op_flags || !d->op_obj)) return fail(MOCHI_EINVAL, "an op array is missing");
+  if (k->n_keys && (!k->key_flags || !k->key_value_off || !k->key_value_len || !k->key_cert_off || !k->key_cert_len))
+    return fail(MOCHI_EINVAL, "a key state array is missing");
+  if (!o->plan_status || !o->resp_kind || !o->resp_n_ops || !o->slot_off)
+    return fail(MOCHI_EINVAL, "plan_status / resp_kind / resp_n_ops / slot_off required");
+  if (d->n_ops && (!o->op_status || !o->op_existed || !o->op_flags || !o->op_result_off || !o->op_result_len ||
+                   !o->op_cert_off || !o->op_cert_len))
+    return fail(MOCHI_EINVAL, "the per-slot outputs are required");
+  return MOCHI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mochi_read_request_decode_bound(uint64_t wire_len, uint32_t n_reqs) {
+  return mochi_write1_request_decode_bound(wire_len, n_reqs);
+}
+
+int mochi_read_request_decode(const mochi_read_requests* r, mochi_read_requests_decoded* o) {
+  int rc = check_read_requests(r, o);
+  if (rc) return rc;
+  const char* err = nullptr;
+  rc = mochi_host::read_request_decode(r, o, &err);
+  if (rc && err) return fail(rc, "mochi_read_request_decode: %s", err);
+  return rc ? rdq_capacity_error(o) : MOCHI_OK;
+}
+
+int mochi_read_request_decode_device(mochi_ctx* c, const mochi_read_requests* r, mochi_read_requests_decoded* o,
+                                     uint32_t* n_keys_dev, void* stream) {
+  if (!c) return fail(MOCHI_EINVAL, "null context");
+  if (!n_keys_dev) return fail(MOCHI_EINVAL, "n_keys_dev required");
+  int rc = check_read_requests(r, o);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard dev(c->device);
+  if (!dev.ok) return fail(MOCHI_EHIP, "hipSetDevice(%d)", c->device);
+  new_call(c);
+  return run_read_request_device(c, r, o, n_keys_dev, (hipStream_t)stream);
+}
+
+int mochi_ctx_read_read_decode_profile(mochi_ctx* c, float* kernel_ms, uint32_t n) {
+  if (!c || !kernel_ms) return fail(MOCHI_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  static const int kSpan[mochi::kRdReqStages][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}};
+  return c->rdq.read_profile(kSpan, mochi::kRdReqStages, kernel_ms, n,
+                             "no read request decode call was made while profiling was on");
+}
+
+int mochi_read_answer_plan(uint32_t n_reqs, const mochi_read_requests_decoded* d, const mochi_read_key_state* k,
+                           mochi_read_answer_planned* o) {
+  int rc = check_read_plan(n_reqs, d, k, o);
+  if (rc || !n_reqs) return rc;
+  const mochi::rdq::PlanView v{n_reqs, *d, *k, *o};
+  const char* err = "";
+  rc = mochi_host::read_answer_plan(&v, &err);
+  return rc ? fail(rc, "mochi_read_answer_plan: %s", err) : MOCHI_OK;
+}
+
+int mochi_read_answer_plan_device(uint32_t n_reqs, const mochi_read_requests_decoded* d, const mochi_read_key_state* k,
+                                  mochi_read_answer_planned* o, void* stream) {
+  int rc = check_read_plan(n_reqs, d, k, o);
+  if (rc || !n_reqs) return rc;
+  const mochi::rdq::PlanView v{n_reqs, *d, *k, *o};
+  HIP_TRY(mochi::launch_rda_plan(v, (hipStream_t)stream));
   return MOCHI_OK;
 }
 

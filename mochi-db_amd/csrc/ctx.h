@@ -204,6 +204,10 @@ struct mochi_ctx {
   mochi::DevBuf w1d_sig;  // ... and its signature sources, sized once the grant total is known
   mochi::EncState rr;   // result reply decoder (result_decode.hip); it waits for no total
   mochi::EncState rae;  // answer encoder (result_encode.hip); its total is the wire size
+  // read request decoder (read_request.hip): the per-request scratch, its total is n_ops; the
+  // per-op scratch (claim table, key numbering) is sized once n_ops is known
+  mochi::EncState rdq;
+  mochi::DevBuf rdq_tab;
   // envelope codec (envelope.hip), one state per call so that each keeps its last profile:
   // decode (events alone), route, join (its `scan` is the radix sort's temp), encode
   mochi::EncState env_dec, env_route, env_join, env_enc;

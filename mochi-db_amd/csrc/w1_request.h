@@ -185,8 +185,9 @@ WIRE_HD void emit_op(const View& v, uint32_t q, uint32_t tx_off, uint32_t tx_len
   v.out.op_flags[o] = action_flags(op.action);
 }
 
-// does the op take part in the key numbering
-WIRE_HD bool has_key(uint8_t flags, uint32_t key_len) { return (flags & kWD) && key_len != 0; }
+// does the op take part in the key numbering: one of `part` among its flags and a non-empty key
+WIRE_HD bool takes_part(uint8_t flags, uint8_t part, uint32_t key_len) { return (flags & part) && key_len != 0; }
+WIRE_HD bool has_key(uint8_t flags, uint32_t key_len) { return takes_part(flags, kWD, key_len); }
 
 // the join, per op (host pointers or device pointers)
 struct JoinArgs {
@@ -223,14 +224,63 @@ WIRE_HD void join_op(const JoinArgs& a, uint32_t o) {
 
 }  // namespace w1q
 
+// The batch-wide key numbering of a request decoder's ops (this one's and read_request.hip's):
+// what k_w1q_claim / k_w1q_rank / k_w1q_number read and write, device pointers.
+struct KeyNumArgs {
+  const uint8_t* wire;
+  const uint64_t* op_key_off;  // [n_ops] into wire
+  const uint32_t* op_key_len;
+  const uint8_t* op_flags;
+  uint8_t part;                // w1q::takes_part's flags
+  uint32_t n_ops, slots;       // slots = w1_table_slots(n_ops)
+  uint32_t* op_obj;            // [n_ops] out
+  uint32_t* key_op;            // [n_keys] out
+  uint32_t* n_keys;            // one word, out
+  // scratch (key_table_layout)
+  uint32_t* tbl_op;    // [slots] the op that claimed the slot, ~0 = empty
+  uint32_t* tbl_min;   // [slots] the smallest op index that reached the slot
+  uint32_t* op_slot;   // [n_ops] the slot of the op's key, ~0 = the op has no key index
+  uint64_t* rep64;     // [n_ops+1] 1 where the op is the first of its key; last = 0
+  uint64_t* key_off;   // [n_ops+1] its exclusive scan; key_off[n_ops] = n_keys
+  void* scan_temp;
+  size_t scan_temp_bytes;
+  // per-kernel timing or null: four events, recorded after the table clear + k_w1q_claim,
+  // after k_w1q_rank, after the key scan, after k_w1q_number
+  hipEvent_t* ev;
+};
+inline size_t key_table_layout(KeyNumArgs& k, void* base) {
+  const size_t o1 = (size_t)k.n_ops + 1;
+  Carve c(base);
+  k.tbl_op = c.take<uint32_t>(k.slots);  // tbl_op and tbl_min adjacent: one fill
+  k.tbl_min = c.take<uint32_t>(k.slots);
+  k.op_slot = c.take<uint32_t>(o1);
+  k.rep64 = c.take<uint64_t>(o1);
+  k.key_off = c.take<uint64_t>(o1);
+  return c.bytes();
+}
+// table clear, claim, rank, scan, number
+hipError_t launch_key_number(const KeyNumArgs& k, hipStream_t stream);
+// The grid-stride entry kernel (k_w1q_ops) of both request decoders: entry e of the e_base[Q]
+// entries is Operation e - e_base[q] of request q's transaction, whose slice is the first two
+// words of the request's eight in l1; a malformed one ORs kStMal into st_bits[q].
+struct EntryArgs {
+  const uint8_t* wire;
+  const uint64_t* msg_off;  // [Q]
+  uint32_t Q;
+  const uint64_t* e_base;   // [Q+1]
+  const uint32_t* l1;       // [Q][8]
+  uint32_t* st_bits;        // [Q]
+};
+hipError_t launch_w1q_ops(const EntryArgs& a, hipStream_t stream);
 // Device pointers; the signer's scratch.  The per-request part (w1q_layout) is laid
-// out before the first launch, the per-op part (w1q_table_layout) once the host knows n_ops.
+// out before the first launch, the per-op part (key_table_layout on k, with k.n_ops and
+// k.slots set) once the host knows n_ops.
 struct W1ReqArgs {
   w1q::View v;
   uint32_t Q;
   uint32_t n_ops;      // set after the host wait
-  uint32_t slots;      // w1_table_slots(n_ops)
   uint32_t* n_keys;    // the caller's device word
+  KeyNumArgs k;        // n_ops, slots and the scratch; launch_w1q_emit fills in the rest
   // per-request scratch
   uint32_t* st_bits;   // [Q] kStMal / kStFb, OR-ed in by the entry lanes
   uint32_t* l1;        // [Q][8] w1q::Level1
@@ -238,12 +288,6 @@ struct W1ReqArgs {
   uint64_t* e_base;    // [Q+1] their exclusive scan; e_base[Q] = the entry total
   uint64_t* cnt64;     // [Q+1] ops per request (0 unless OK)
   uint64_t* off64;     // [Q+1] its exclusive scan; off64[Q] = n_ops
-  // per-op scratch
-  uint32_t* tbl_op;    // [slots] the op that claimed the slot, ~0 = empty
-  uint32_t* tbl_min;   // [slots] the smallest op index that reached the slot
-  uint32_t* op_slot;   // [n_ops] the slot of the op's key, ~0 = the op has no key index
-  uint64_t* rep64;     // [n_ops+1] 1 where the op is the first of its key; last = 0
-  uint64_t* key_off;   // [n_ops+1] its exclusive scan; key_off[n_ops] = n_keys
   void* scan_temp;
   size_t scan_temp_bytes;
   // per-kernel timing or null: kW1ReqEvents events, recorded before k_w1q_req, after it,
@@ -254,9 +298,9 @@ struct W1ReqArgs {
 };
 constexpr int kW1ReqEvents = 11;
 constexpr int kW1ReqStages = 9;
-// The scratch layouts (a.Q / a.n_ops and a.slots set; every array 16-byte aligned): on a
+// The scratch layouts (a.Q, or k.n_ops and k.slots, set; every array 16-byte aligned): on a
 // null base they only count and return the bytes to allocate; on that allocation they
-// set a's scratch pointers.
+// set the scratch pointers.
 inline size_t w1q_layout(W1ReqArgs& a, void* base) {
   const size_t Q = a.Q, q1 = Q + 1;
   Carve c(base);
@@ -266,16 +310,6 @@ inline size_t w1q_layout(W1ReqArgs& a, void* base) {
   a.e_base = c.take<uint64_t>(q1);
   a.cnt64 = c.take<uint64_t>(q1);
   a.off64 = c.take<uint64_t>(q1);
-  return c.bytes();
-}
-inline size_t w1q_table_layout(W1ReqArgs& a, void* base) {
-  const size_t o1 = (size_t)a.n_ops + 1;
-  Carve c(base);
-  a.tbl_op = c.take<uint32_t>(a.slots);  // tbl_op and tbl_min adjacent: one fill
-  a.tbl_min = c.take<uint32_t>(a.slots);
-  a.op_slot = c.take<uint32_t>(o1);
-  a.rep64 = c.take<uint64_t>(o1);
-  a.key_off = c.take<uint64_t>(o1);
   return c.bytes();
 }
 // framing, validation, statuses, per-request outputs and req_op_off; off64[Q] = n_ops

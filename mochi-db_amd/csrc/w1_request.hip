@@ -26,6 +26,10 @@
 //   k_w1q_number   op_obj, key_op, *n_keys
 //   k_w1q_join     lane = op: the key's state onto the op (mochi_write1_state_join_device)
 //
+// k_w1q_ops and the key numbering (k_w1q_claim, k_w1q_rank, k_w1q_number) take narrow
+// argument structs (EntryArgs, KeyNumArgs): the ReadToServer decoder (read_request.hip)
+// launches the same kernels through launch_w1q_ops and launch_key_number.
+//
 // The hash decides no output: keys are numbered by their first op in op order.  The
 // walk itself is w1_request.h's, shared with the host form.  Every read of a body goes
 // through its (base, length): lengths are the sender's.
@@ -59,8 +63,7 @@ __global__ __launch_bounds__(256) void k_w1q_req(W1ReqArgs a) {
   a.cnt_e[q] = bits ? 0 : o.n_ent;
 }
 
-__global__ __launch_bounds__(256) void k_w1q_ops(W1ReqArgs a) {
-  const mochi_write1_requests& in = a.v.in;
+__global__ __launch_bounds__(256) void k_w1q_ops(EntryArgs a) {
   const uint64_t total = a.e_base[a.Q];
 #pragma unroll 1
   for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (uint64_t)gridDim.x * blockDim.x) {
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(256) void k_w1q_ops(W1ReqArgs a) {
       else hi = mid;
     }
     const uint32_t q = lo, j = (uint32_t)(e - a.e_base[q]);
-    const uint8_t* b = in.wire + in.msg_off[q];
+    const uint8_t* b = a.wire + a.msg_off[q];
     const uint4 l = ((const uint4*)a.l1)[2 * q];
     uint32_t eo, el;
     tx_entry(b, l.x, l.y, j, eo, el);
@@ -118,22 +121,21 @@ __device__ __forceinline__ uint32_t key_slot(const uint8_t* __restrict__ k, uint
   return wire::bytes_hash(k, n) & mask;
 }
 
-__global__ __launch_bounds__(256) void k_w1q_claim(W1ReqArgs a) {
+__global__ __launch_bounds__(256) void k_w1q_claim(KeyNumArgs a) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= a.n_ops) return;
-  const mochi_write1_requests_decoded& out = a.v.out;
-  const uint32_t kl = out.op_key_len[o], mask = a.slots - 1;
+  const uint32_t kl = a.op_key_len[o], mask = a.slots - 1;
   uint32_t slot = kNone;
-  if (has_key(out.op_flags[o], kl)) {
-    const uint8_t* k = a.v.in.wire + out.op_key_off[o];
+  if (takes_part(a.op_flags[o], a.part, kl)) {
+    const uint8_t* k = a.wire + a.op_key_off[o];
     uint32_t h = key_slot(k, kl, mask);
     // at most n_ops keys in >= 2 * n_ops slots: a free or equal slot is met within `mask` steps
 #pragma unroll 1
     for (uint32_t n = 0; n <= mask; n++, h = (h + 1) & mask) {
       const uint32_t prev = atomicCAS(&a.tbl_op[h], kNone, o);
-      // the claimer's slice was written by k_w1q_emit, a launch ago
+      // the claimer's slice was written by the emit kernel, a launch ago
       if (prev == kNone || prev == o ||
-          (out.op_key_len[prev] == kl && wire::bytes_eq(a.v.in.wire + out.op_key_off[prev], k, kl))) {
+          (a.op_key_len[prev] == kl && wire::bytes_eq(a.wire + a.op_key_off[prev], k, kl))) {
         atomicMin(&a.tbl_min[h], o);
         slot = h;
         break;
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256) void k_w1q_claim(W1ReqArgs a) {
   a.op_slot[o] = slot;
 }
 
-__global__ __launch_bounds__(256) void k_w1q_rank(W1ReqArgs a) {
+__global__ __launch_bounds__(256) void k_w1q_rank(KeyNumArgs a) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o > a.n_ops) return;
   if (o == a.n_ops) {
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void k_w1q_rank(W1ReqArgs a) {
   a.rep64[o] = s != kNone && a.tbl_min[s] == o ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_w1q_number(W1ReqArgs a) {
+__global__ __launch_bounds__(256) void k_w1q_number(KeyNumArgs a) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o == 0) *a.n_keys = (uint32_t)a.key_off[a.n_ops];
   if (o >= a.n_ops) return;
@@ -163,9 +165,9 @@ __global__ __launch_bounds__(256) void k_w1q_number(W1ReqArgs a) {
   if (s != kNone) {
     const uint32_t rep = a.tbl_min[s];
     u = (uint32_t)a.key_off[rep];
-    if (rep == o) a.v.out.key_op[u] = o;
+    if (rep == o) a.key_op[u] = o;
   }
-  a.v.out.op_obj[o] = u;
+  a.op_obj[o] = u;
 }
 
 __global__ __launch_bounds__(256) void k_w1q_join(JoinArgs a) {
@@ -185,8 +187,9 @@ hipError_t launch_w1q_count(const W1ReqArgs& a, hipStream_t st) {
   if ((e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.cnt_e, a.e_base, a.Q + 1, st)) != hipSuccess ||
       (e = stamp(2)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(k_w1q_ops, dim3(w1q_ops_blocks(a.Q)), dim3(256), 0, st, a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(3)) != hipSuccess) return e;
+  if ((e = launch_w1q_ops(EntryArgs{a.v.in.wire, a.v.in.msg_off, a.Q, a.e_base, a.l1, a.st_bits}, st)) != hipSuccess ||
+      (e = stamp(3)) != hipSuccess)
+    return e;
   hipLaunchKernelGGL(k_w1q_final, dim3(g1), dim3(256), 0, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.cnt64, a.off64, a.Q + 1, st)) != hipSuccess) return e;
@@ -195,26 +198,51 @@ hipError_t launch_w1q_count(const W1ReqArgs& a, hipStream_t st) {
   return stamp(4);
 }
 
-hipError_t launch_w1q_emit(const W1ReqArgs& a, hipStream_t st) {
+hipError_t launch_w1q_ops(const EntryArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(k_w1q_ops, dim3(w1q_ops_blocks(a.Q)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_key_number(const KeyNumArgs& a, hipStream_t st) {
   const Stamps stamp{a.ev, st};
   const uint32_t O = a.n_ops, g0 = cdiv(O, 256), g1 = cdiv((uint64_t)O + 1, 256);
   hipError_t e;
-  if ((e = stamp(5)) != hipSuccess) return e;
-  if (O) hipLaunchKernelGGL(k_w1q_emit, dim3(g0), dim3(256), 0, st, a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(6)) != hipSuccess) return e;
   // every slot empty, every minimum "no op"
   if ((e = hipMemsetAsync(a.tbl_op, 0xFF, (size_t)((uint8_t*)(a.tbl_min + a.slots) - (uint8_t*)a.tbl_op), st)) != hipSuccess)
     return e;
   if (O) hipLaunchKernelGGL(k_w1q_claim, dim3(g0), dim3(256), 0, st, a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(7)) != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(0)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_w1q_rank, dim3(g1), dim3(256), 0, st, a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(8)) != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(1)) != hipSuccess) return e;
   if ((e = enc_scan64(a.scan_temp, a.scan_temp_bytes, a.rep64, a.key_off, O + 1, st)) != hipSuccess ||
-      (e = stamp(9)) != hipSuccess)
+      (e = stamp(2)) != hipSuccess)
     return e;
   hipLaunchKernelGGL(k_w1q_number, dim3(g1), dim3(256), 0, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return stamp(10);
+  return stamp(3);
+}
+
+hipError_t launch_w1q_emit(const W1ReqArgs& a, hipStream_t st) {
+  const Stamps stamp{a.ev, st};
+  const uint32_t O = a.n_ops;
+  hipError_t e;
+  if ((e = stamp(5)) != hipSuccess) return e;
+  if (O) hipLaunchKernelGGL(k_w1q_emit, dim3(cdiv(O, 256)), dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess || (e = stamp(6)) != hipSuccess) return e;
+  const mochi_write1_requests_decoded& out = a.v.out;
+  KeyNumArgs k = a.k;  // n_ops, slots and the table from the caller
+  k.wire = a.v.in.wire;
+  k.op_key_off = out.op_key_off;
+  k.op_key_len = out.op_key_len;
+  k.op_flags = out.op_flags;
+  k.part = kWD;
+  k.op_obj = out.op_obj;
+  k.key_op = out.key_op;
+  k.n_keys = a.n_keys;
+  k.scan_temp = a.scan_temp;
+  k.scan_temp_bytes = a.scan_temp_bytes;
+  k.ev = a.ev ? a.ev + 7 : nullptr;
+  return launch_key_number(k, st);
 }
 
 hipError_t launch_w1q_join(const JoinArgs& a, hipStream_t st) {

@@ -229,6 +229,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_ctx_read_result_encode_profile.argtypes = [vp, vp, u32]
     lib.mochi_write2_answer_plan.argtypes = [vp, vp, vp]
     lib.mochi_write2_answer_plan_device.argtypes = [vp, vp, vp, vp]
+    lib.mochi_read_request_decode_bound.restype = u64
+    lib.mochi_read_request_decode_bound.argtypes = [u64, u32]
+    lib.mochi_read_request_decode.argtypes = [vp, vp]
+    lib.mochi_read_request_decode_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mochi_ctx_read_read_decode_profile.argtypes = [vp, vp, u32]
+    lib.mochi_read_answer_plan.argtypes = [u32, vp, vp, vp]
+    lib.mochi_read_answer_plan_device.argtypes = [u32, vp, vp, vp, vp]
     lib.mochi_envelope_decode.argtypes = [vp, vp]
     lib.mochi_envelope_decode_device.argtypes = [vp, vp, vp, vp]
     lib.mochi_envelope_route.argtypes = [u32, vp, vp, vp, vp, vp]
@@ -654,6 +661,28 @@ class Verifier:
         if self.lib.mochi_ctx_read_result_encode_profile(self.ctx, _ptr(ms), ms.size) != OK:
             raise MochiError(f"mochi_ctx_read_result_encode_profile: {_err(self.lib)}")
         return dict(zip(RESULT_ENCODE_STAGES, (float(x) for x in ms)))
+
+    def read_request_decode_device(self, dreqs: "DeviceReadRequests", out: "DeviceReadRequestsDecoded", stream: int = 0,
+                                   check: bool = True) -> int:
+        """mochi_read_request_decode_device: ReadToServer bodies in device memory to SoA arrays
+        with their key numbering, in device memory.  Sets out.n_ops (the key count goes to the
+        device word out.n_keys_dev); returns the rc, EINVAL when out.op_cap is too small
+        (raises then if `check`)."""
+        r, o = dreqs.to_c(), out.to_c()
+        rc = self.lib.mochi_read_request_decode_device(self.ctx, ctypes.addressof(r), ctypes.addressof(o),
+                                                       out.n_keys_dev.data_ptr(), stream or None)
+        out.n_ops = int(o.n_ops)
+        short = rc == EINVAL and out.n_ops > out.op_cap
+        if rc != OK and (check or not short):
+            raise MochiError(f"mochi_read_request_decode_device rc={rc}: {_err(self.lib)}")
+        return rc
+
+    def read_read_decode_profile(self) -> dict:
+        """Per-kernel ms of the last read_request_decode_device call made with set_profiling(True)."""
+        ms = np.zeros(len(READ_REQUEST_STAGES), np.float32)
+        if self.lib.mochi_ctx_read_read_decode_profile(self.ctx, _ptr(ms), ms.size) != OK:
+            raise MochiError(f"mochi_ctx_read_read_decode_profile: {_err(self.lib)}")
+        return dict(zip(READ_REQUEST_STAGES, (float(x) for x in ms)))
 
     def envelope_decode_device(self, dframes: "DeviceEnvelopeFrames", out: "DeviceEnvelopeDecoded",
                                stream: int = 0) -> None:
@@ -2963,6 +2992,249 @@ def write2_answer_plan_device(dwb: "DeviceWireBatch", verdicts: "DeviceVerdicts"
     rc = lib.mochi_write2_answer_plan_device(ctypes.addressof(b), ctypes.addressof(s), ctypes.addressof(o), stream or None)
     if rc != OK:
         raise MochiError(f"mochi_write2_answer_plan_device rc={rc}: {_err(lib)}")
+
+
+# ---------------------------------------------------------------------------
+# Read request decode and read answer plan (the server's side of a read): ReadToServer
+# bodies -> SoA arrays with their batch-wide key numbering; those and the store's state
+# per distinct key -> the answer encoder's input
+# ---------------------------------------------------------------------------
+RDQ_OK, RDQ_MALFORMED, RDQ_FALLBACK = range(3)
+RDOP_READ = 0x01
+RDA_REPLY, RDA_NO_REPLY, RDA_HOST = range(3)
+RDK_LOCAL, RDK_PRESENT, RDK_AVAILABLE, RDK_HAS_CERT = 0x01, 0x02, 0x04, 0x08
+READ_REQUEST_STAGES = ("k_rdq_req", "entry_scan", "k_w1q_ops", "final_scan_offsets", "k_rdq_emit", "k_w1q_claim",
+                       "k_w1q_rank", "key_scan", "k_w1q_number")
+
+ReadRequests = Write1Requests  # mochi_read_requests is mochi_write1_requests
+DeviceReadRequests = DeviceWrite1Requests
+
+# output arrays by what they are indexed with, as _W1Q_OUT
+_RDQ_OUT = dict(req_status=(np.uint8, "Q"), req_client_off=(np.uint64, "Q"), req_client_len=(np.uint32, "Q"),
+                req_nonce_off=(np.uint64, "Q"), req_nonce_len=(np.uint32, "Q"), req_op_off=(np.uint32, "Q1"),
+                op_key_off=(np.uint64, "O"), op_key_len=(np.uint32, "O"), op_flags=(np.uint8, "O"),
+                op_obj=(np.uint32, "O"), key_op=(np.uint32, "K"))
+_RDK_IN = dict(key_flags=np.uint8, key_value_off=np.uint64, key_value_len=np.uint32, key_cert_off=np.uint64,
+               key_cert_len=np.uint32)
+# the outputs of the read answer plan: "Q" per request, "S" per slot (= per op)
+_RDA_OUT = dict(plan_status=(np.uint8, "Q"), resp_kind=(np.uint8, "Q"), resp_n_ops=(np.uint32, "Q"),
+                slot_off=(np.uint64, "Q"), **{k: _RA_IN[k] for k in _RA_SLOT})
+
+
+class ReadRequestsDecoded_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("req_status", "req_client_off", "req_client_len", "req_nonce_off",
+                                               "req_nonce_len", "req_op_off")] + \
+        [("n_ops", ctypes.c_uint32), ("n_keys", ctypes.c_uint32), ("op_cap", ctypes.c_uint32), ("_pad0", ctypes.c_uint32)] + \
+        [(k, ctypes.c_void_p) for k in ("op_key_off", "op_key_len", "op_flags", "op_obj", "key_op")]
+
+
+class ReadKeyState_C(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_uint32), ("_pad0", ctypes.c_uint32)] + [(k, ctypes.c_void_p) for k in _RDK_IN] + \
+        [("store_len", ctypes.c_uint64)]
+
+
+class ReadAnswerPlanned_C(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _RDA_OUT]
+
+
+@dataclass
+class ReadRequestsDecoded:
+    """Outputs of read_request_decode (mochi_read_requests_decoded): the caller's buffers,
+    whole (n_ops / n_keys say how much of the per-op ones / of key_op is meant)."""
+
+    rc: int
+    n_ops: int
+    n_keys: int
+    arrays: dict  # name -> array, names as in mochi_read_requests_decoded
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def trimmed(self) -> dict:
+        """Every array cut to its meaning (per-op ones and key_op to 0 unless rc is OK)."""
+        Q = self.arrays["req_status"].shape[0]
+        ok = self.rc == OK
+        n = dict(Q=Q, Q1=Q + 1, O=self.n_ops if ok else 0, K=self.n_keys if ok else 0)
+        return {k: self.arrays[k][:n[w]] for k, (dt, w) in _RDQ_OUT.items()}
+
+
+def read_request_decode_bound(wire_len: int, n_reqs: int) -> int:
+    """mochi_read_request_decode_bound: a safe op_cap."""
+    return int(load_library().mochi_read_request_decode_bound(int(wire_len), int(n_reqs)))
+
+
+def read_request_decode_into(reqs: "ReadRequests", op_cap: int, fill: int = 0) -> "ReadRequestsDecoded":
+    """mochi_read_request_decode into buffers of the given capacity, prefilled with `fill`.
+    rc is EINVAL with n_ops = the count needed when it is too small (no per-op array
+    touched); any other failure raises."""
+    lib = load_library()
+    r, keep = reqs.to_c()
+    Q = reqs.n_reqs
+    n = dict(Q=Q, Q1=Q + 1, O=int(op_cap), K=int(op_cap))
+    arr = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _RDQ_OUT.items()}
+    o = ReadRequestsDecoded_C()
+    for k, a in arr.items():
+        setattr(o, k, _ptr(a) if a.size else None)
+    o.op_cap = int(op_cap)
+    rc = lib.mochi_read_request_decode(ctypes.addressof(r), ctypes.addressof(o))
+    if rc != OK and not (rc == EINVAL and o.n_ops > op_cap):
+        raise MochiError(f"mochi_read_request_decode rc={rc}: {_err(lib)}")
+    return ReadRequestsDecoded(rc=rc, n_ops=int(o.n_ops), n_keys=int(o.n_keys), arrays=arr)
+
+
+def read_request_decode(reqs: "ReadRequests") -> "ReadRequestsDecoded":
+    """Host form of the read request decoder: the count first, then into buffers of exactly
+    the size needed."""
+    first = read_request_decode_into(reqs, 0)
+    if first.rc == OK:
+        return first
+    return read_request_decode_into(reqs, first.n_ops)
+
+
+@dataclass
+class ReadKeyState:
+    """The store's state per distinct key of a decoded read batch (mochi_read_key_state, host
+    arrays) and the blob its slices point into."""
+
+    store: np.ndarray  # uint8
+    key_flags: np.ndarray  # uint8 [U] RDK_*
+    key_value_off: np.ndarray  # uint64 [U]
+    key_value_len: np.ndarray  # uint32 [U]
+    key_cert_off: np.ndarray  # uint64 [U]
+    key_cert_len: np.ndarray  # uint32 [U]
+
+    def arrays(self) -> dict:
+        d = {k: np.ascontiguousarray(getattr(self, k), dt).reshape(-1) for k, dt in _RDK_IN.items()}
+        d["store"] = np.ascontiguousarray(self.store, np.uint8).reshape(-1)
+        return d
+
+
+def read_answer_plan(dec: "ReadRequestsDecoded", keys: "ReadKeyState", fill: int = 0) -> dict:
+    """mochi_read_answer_plan (host form) over a decoded batch (its arrays trimmed or whole):
+    the arrays of mochi_read_answer_planned by name, over buffers prefilled with `fill`."""
+    lib = load_library()
+    some = lambda a, dt: np.ascontiguousarray(a if np.asarray(a).size else np.zeros(1, dt), dt).reshape(-1)
+    Q = int(np.asarray(dec.arrays["req_status"]).shape[0])
+    d = ReadRequestsDecoded_C()
+    ins = {k: some(dec.arrays[k], _RDQ_OUT[k][0]) for k in ("req_status", "req_op_off", "op_key_len", "op_flags", "op_obj")}
+    for k, a in ins.items():
+        setattr(d, k, _ptr(a))
+    d.n_ops = int(dec.n_ops)
+    karr = keys.arrays()
+    ks = ReadKeyState_C()
+    ks.n_keys, ks.store_len = int(karr["key_flags"].size), int(karr["store"].size)
+    for k in _RDK_IN:
+        karr[k] = some(karr[k], _RDK_IN[k])
+        setattr(ks, k, _ptr(karr[k]))
+    n = dict(Q=Q, S=int(dec.n_ops))
+    out = {k: np.full(n[w] * np.dtype(dt).itemsize, fill, np.uint8).view(dt) for k, (dt, w) in _RDA_OUT.items()}
+    o = ReadAnswerPlanned_C()
+    for k, a in out.items():
+        setattr(o, k, _ptr(a if a.size else np.zeros(1, a.dtype)))
+    rc = lib.mochi_read_answer_plan(Q, ctypes.addressof(d), ctypes.addressof(ks), ctypes.addressof(o))
+    if rc != OK:
+        raise MochiError(f"mochi_read_answer_plan rc={rc}: {_err(lib)}")
+    return out
+
+
+def read_planned_answers(wire, store, planned: dict, nonce_off, nonce_len, ids=None, rid_off=None,
+                         rid_len=None) -> "ResultAnswers":
+    """The read plan's outputs as the encoder's input (host arrays): ids = wire unless given,
+    the nonces the decoder's req_nonce_off / req_nonce_len."""
+    return ResultAnswers(wire=wire, store=store, ids=wire if ids is None else ids, resp_kind=planned["resp_kind"],
+                         resp_n_ops=planned["resp_n_ops"], slot_off=planned["slot_off"], rid_off=rid_off, rid_len=rid_len,
+                         nonce_off=nonce_off, nonce_len=nonce_len, **{k: planned[k] for k in _RA_SLOT})
+
+
+class DeviceReadRequestsDecoded:
+    """Device buffers for the outputs of Verifier.read_request_decode_device, prefilled with
+    `fill`; n_ops is set by the call, the key count lands in the device word n_keys_dev.
+    Tensors carry the ABI widths (uint32 as int32, uint64 as int64)."""
+
+    def __init__(self, n_reqs: int, op_cap: int, device: int = 0, fill: int = 0):
+        self.n_reqs, self.op_cap = int(n_reqs), int(op_cap)
+        n = dict(Q=self.n_reqs, Q1=self.n_reqs + 1, O=self.op_cap, K=self.op_cap)
+        for k, (dt, w) in _RDQ_OUT.items():
+            setattr(self, k, _dev_full(n[w], dt, fill, device))
+        self.n_keys_dev = _dev_full(1, np.uint32, fill, device)
+        self.n_ops = 0
+
+    def to_c(self) -> ReadRequestsDecoded_C:
+        o = ReadRequestsDecoded_C()
+        for k in _RDQ_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        o.op_cap, o.n_ops = self.op_cap, self.n_ops
+        return o
+
+    def n_keys(self) -> int:
+        """The key count (a device read: synchronises)."""
+        return int(self.n_keys_dev.cpu().numpy().view(np.uint32)[0])
+
+    def to_host(self, rc: int = OK) -> "ReadRequestsDecoded":
+        """The buffers on the host, whole (as read_request_decode_into returns them)."""
+        n = dict(Q=self.n_reqs, Q1=self.n_reqs + 1, O=self.op_cap, K=self.op_cap)
+        arr = {k: getattr(self, k).cpu().numpy().view(dt)[:n[w]] for k, (dt, w) in _RDQ_OUT.items()}
+        return ReadRequestsDecoded(rc=rc, n_ops=self.n_ops, n_keys=self.n_keys(), arrays=arr)
+
+
+class DeviceReadKeyState:
+    """A ReadKeyState copied into device memory with torch (plumbing only)."""
+
+    def __init__(self, keys: "ReadKeyState", device: int = 0):
+        a = keys.arrays()
+        self.n_keys, self.store_len = int(a["key_flags"].size), int(a["store"].size)
+        for k, v in a.items():
+            setattr(self, k, _to_dev(v, device))
+
+    def to_c(self) -> ReadKeyState_C:
+        c = ReadKeyState_C()
+        c.n_keys, c.store_len = self.n_keys, self.store_len
+        for k in _RDK_IN:
+            setattr(c, k, getattr(self, k).data_ptr())
+        return c
+
+
+class DeviceReadAnswerPlanned:
+    """Device buffers for the outputs of read_answer_plan_device, prefilled with `fill`
+    (n_slots: the decoder's n_ops or more)."""
+
+    def __init__(self, n_reqs: int, n_slots: int, device: int = 0, fill: int = 0):
+        self.n = dict(Q=int(n_reqs), S=int(n_slots))
+        for k, (dt, w) in _RDA_OUT.items():
+            setattr(self, k, _dev_full(self.n[w], dt, fill, device))
+
+    def to_c(self) -> ReadAnswerPlanned_C:
+        o = ReadAnswerPlanned_C()
+        for k in _RDA_OUT:
+            setattr(o, k, getattr(self, k).data_ptr())
+        return o
+
+    def to_host(self) -> dict:
+        return {k: getattr(self, k).cpu().numpy().view(dt)[:self.n[w]] for k, (dt, w) in _RDA_OUT.items()}
+
+    def answers(self, dreqs: "DeviceReadRequests", dec: "DeviceReadRequestsDecoded", dkeys: "DeviceReadKeyState",
+                rid_off=None, rid_len=None) -> "DeviceResultAnswers":
+        """The encoder's input over these buffers, ids = wire and the nonces the decoder's: no
+        copy, no host round trip."""
+        return DeviceResultAnswers.from_tensors(
+            self.n["Q"], dec.n_ops, dec.n_ops, wire=dreqs.wire, store=dkeys.store, ids=dreqs.wire,
+            resp_kind=self.resp_kind, resp_n_ops=self.resp_n_ops, slot_off=self.slot_off, rid_off=rid_off, rid_len=rid_len,
+            nonce_off=dec.req_nonce_off, nonce_len=dec.req_nonce_len, **{k: getattr(self, k) for k in _RA_SLOT})
+
+
+def read_answer_plan_device(dec: "DeviceReadRequestsDecoded", dkeys: "DeviceReadKeyState",
+                            out: "DeviceReadAnswerPlanned", stream: int = 0) -> None:
+    """mochi_read_answer_plan_device: one kernel on `stream`, no wait; reads the decoder's
+    arrays in stream order (dec.n_ops is the host field the decode call set)."""
+    lib = load_library()
+    d, k, o = dec.to_c(), dkeys.to_c(), out.to_c()
+    rc = lib.mochi_read_answer_plan_device(dec.n_reqs, ctypes.addressof(d), ctypes.addressof(k), ctypes.addressof(o),
+                                           stream or None)
+    if rc != OK:
+        raise MochiError(f"mochi_read_answer_plan_device rc={rc}: {_err(lib)}")
 
 
 # ---------------------------------------------------------------------------
