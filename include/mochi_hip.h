@@ -511,6 +511,17 @@ typedef struct mochi_write2_decoded {
 int mochi_write2_decode(mochi_ctx* ctx, const mochi_write2_batch* batch, mochi_write2_decoded* out);
 void mochi_write2_decoded_free(mochi_write2_decoded* d);
 
+/* mochi_write2_decode, and with it the decoder's first-grant hint (additive; inspection
+ * and tests: the verify path hands the hint to grant prep and never copies it back).
+ * *grant_same receives [n_grants] indices into the decoded grants of the whole batch,
+ * allocated by the library (release with mochi_write2_same_free; NULL on failure):
+ * grant_same[g] is g itself, or the first decoded grant of g's message -- then that
+ * grant lies before g and its bytes are g's, byte for byte.  A NULL grant_same makes
+ * the call mochi_write2_decode. */
+int mochi_write2_decode_same(mochi_ctx* ctx, const mochi_write2_batch* batch, mochi_write2_decoded* out,
+                             uint32_t** grant_same);
+void mochi_write2_same_free(uint32_t* grant_same);
+
 /* ------------------------------------------------------------------------
  * Write2ToServer ENCODE: the inverse of the decoder above, the client's
  * certificate assembly (MochiDBClient.java:333-338).  An SoA batch of the

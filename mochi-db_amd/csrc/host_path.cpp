@@ -515,7 +515,7 @@ enum W2Seg { kW2Wire, kW2MsgOff, kW2MsgLen, kW2OpFlagsOff, kW2OpFlags, kW2OpObjT
 enum W2Out { kW2Acc, kW2Reason, kW2Fail, kW2Status, kW2Dec, kW2G0, kW2OpTs, kNumW2Out };
 
 static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const mochi_params* p, mochi_verdicts* o,
-                              uint8_t* msg_status, mochi_write2_decoded* dec) {
+                              uint8_t* msg_status, mochi_write2_decoded* dec, uint32_t** same = nullptr) {
   constexpr size_t kW2Lag = 2;  // chunks counted ahead of the one being verified
   int rc;
   const uint32_t M = w->n_msgs;
@@ -678,6 +678,12 @@ static int verify_write2_host(mochi_ctx* c, const mochi_write2_batch* w, const m
               {dec->op_key_off, da.op_key_off, 8 * (size_t)O},   {dec->op_key_len, da.op_key_len, 4 * (size_t)O}};
     for (auto& x : cp)
       if (x.n) HIP_TRY(hipMemcpyAsync(x.dst, x.src, x.n, hipMemcpyDeviceToHost, st));
+    if (same) {
+      // the first-grant hint as prep reads it: indices relative to the launch, and the
+      // decode-only call is one launch (target above), so they are batch-global as they are
+      *same = (uint32_t*)malloc(4 * (size_t)N + 4);
+      if (N) HIP_TRY(hipMemcpyAsync(*same, da.grant_same, 4 * (size_t)N, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     return MOCHI_OK;
   }
@@ -701,8 +707,14 @@ int mochi_verify_write2(mochi_ctx* c, const mochi_write2_batch* w, const mochi_p
 }
 
 int mochi_write2_decode(mochi_ctx* c, const mochi_write2_batch* w, mochi_write2_decoded* out) {
+  return mochi_write2_decode_same(c, w, out, nullptr);
+}
+
+int mochi_write2_decode_same(mochi_ctx* c, const mochi_write2_batch* w, mochi_write2_decoded* out,
+                             uint32_t** grant_same) {
   if (!out) return fail(MOCHI_EINVAL, "null argument");
   memset(out, 0, sizeof *out);
+  if (grant_same) *grant_same = nullptr;
   mochi_params p = {1, 1, 0, 0};
   mochi_verdicts o;
   memset(&o, 0, sizeof o);
@@ -710,8 +722,10 @@ int mochi_write2_decode(mochi_ctx* c, const mochi_write2_batch* w, mochi_write2_
   o.cert_accept_bits = &dummy;
   int rc = check_write2_header(c, w, &p, &o);
   if (rc) return rc;
-  return verify_write2_host(c, w, &p, &o, nullptr, out);
+  return verify_write2_host(c, w, &p, &o, nullptr, out, grant_same);
 }
+
+void mochi_write2_same_free(uint32_t* grant_same) { free(grant_same); }
 
 void mochi_write2_decoded_free(mochi_write2_decoded* d) {
   if (!d) return;

@@ -178,8 +178,11 @@ __global__ __launch_bounds__(256) MOCHI_PREP_ATTR void k_grant_prep_cert(const P
         if (p.grant_key[h] != s) continue;
         if (a.glen[h] != lg) continue;
         const uint64_t oh = a.goff[h];
-        // the decoder's match (`same`) is taken only with equal lengths as well; with
-        // MOCHI_SAME_HINT_CHECK=1 (a CI build) it must also survive the byte compare
+        // the decoder's match (`same`) is taken only with equal lengths as well, and is
+        // trusted: tests/test_w2_same_hint_gpu.py reads it back (mochi_write2_decode_same)
+        // and pins it to the grant bytes, one differing byte at every position of the
+        // compare.  MOCHI_SAME_HINT_CHECK=1 (A/B, no build sets it) ignores the hint, so
+        // every follower is byte-compared instead
         const bool hinted = p.same && p.same[h] == g && !MOCHI_SAME_HINT_CHECK;
         const bool known = hinted || oh == og;
         if (via_lds && !known && lg <= kMatchMaxLen) {  // compared by k_grant_match

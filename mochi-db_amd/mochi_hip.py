@@ -181,6 +181,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.mochi_verify_write2_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mochi_write2_decode.argtypes = [vp, vp, vp]
     lib.mochi_write2_decoded_free.argtypes = [vp]
+    lib.mochi_write2_decode_same.argtypes = [vp, vp, vp, vp]
+    lib.mochi_write2_same_free.argtypes = [vp]
+    lib.mochi_write2_same_free.restype = None
     lib.mochi_write2_encode_bound.restype = ctypes.c_uint64
     lib.mochi_write2_encode_bound.argtypes = [vp, u32]
     lib.mochi_write2_encode.argtypes = [vp, vp, vp, u32, vp, ctypes.c_uint64, vp, vp, vp, vp]
@@ -736,12 +739,15 @@ class Verifier:
         return dict(zip(names, (float(x) for x in ms)))
 
     def decode_write2(self, wb) -> dict:
-        """The device decoder's SoA view of the messages (inspection / tests)."""
+        """The device decoder's SoA view of the messages (inspection / tests), and under
+        "grant_same" its first-grant hint to grant prep ([n_grants], mochi_write2_decode_same)."""
         wc, keep = write2_batch_c(wb)
         d = Write2Decoded_C()
-        rc = self.lib.mochi_write2_decode(self.ctx, ctypes.addressof(wc), ctypes.addressof(d))
+        same = ctypes.c_void_p()
+        rc = self.lib.mochi_write2_decode_same(self.ctx, ctypes.addressof(wc), ctypes.addressof(d),
+                                               ctypes.addressof(same))
         if rc != OK:
-            raise MochiError(f"mochi_write2_decode rc={rc}: {_err(self.lib)}")
+            raise MochiError(f"mochi_write2_decode_same rc={rc}: {_err(self.lib)}")
         N, M, O = d.n_grants, d.n_msgs, d.n_ops
 
         def arr(ptr, n, dt):
@@ -757,8 +763,10 @@ class Verifier:
                    op_flags=arr(d.op_flags, O, np.uint8), msg_status=arr(d.msg_status, M, np.uint8),
                    cert_mg_off=arr(d.cert_mg_off, M + 1, np.uint32),
                    mg_grant_off=arr(d.mg_grant_off, d.n_mgs + 1, np.uint32),
-                   op_key_off=arr(d.op_key_off, O, np.uint64), op_key_len=arr(d.op_key_len, O, np.uint32))
+                   op_key_off=arr(d.op_key_off, O, np.uint64), op_key_len=arr(d.op_key_len, O, np.uint32),
+                   grant_same=arr(same, N, np.uint32))
         self.lib.mochi_write2_decoded_free(ctypes.addressof(d))
+        self.lib.mochi_write2_same_free(same)
         return out
 
     def set_small_batch(self, grants: int) -> None:
